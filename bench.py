@@ -6,8 +6,8 @@ halo-exchange latency".  The headline ``value`` is the whole-job stencil rate
 in MLUPS (million lattice-point updates per second, summed over all GPUs) on
 the BASELINE multi-GPU config "mpi_stencil2d 32768² ... (2×4 decomp), halo
 exchange/interior overlap".  The global domain is FIXED at 32768² for every N
-(strong scaling: N = 8 is exactly the named config).  The same JSON line
-carries every other BASELINE quantity:
+(strong scaling: N = 8 is exactly the named config).  With ``--full`` the
+same JSON line carries every other BASELINE quantity:
 
 * ``stencil_8192_MLUPS``: the same engine on the 8192² domain (BASELINE
   "mpi_stencil2d 8192² fp64 single GPU" at N = 1);
@@ -31,13 +31,23 @@ every pass type of it is launched once before the warm-up
 Nothing is skipped inside the timed region: K steps are K sweeps of every
 lattice point.
 
-Before timing, every run checks its decomposition: the engine with the same
-process grid and K runs a small domain and is compared with the serial NumPy
-reference (``check_max_diff``, must be 0 — the engine is bitwise); a
-mismatch exits non-zero.
+A plain run does only what the headline needs: it sets the engine up, warms
+up, times the K steps, writes the final field if ``--dump-outputs DIR`` is
+given (``DIR/u.npy``, or a fixed seeded sample of a field too large for 64 MB:
+``DIR/u_sample.npy`` and the sampled points' flat global indices in
+``DIR/u_sample_index.npy``) and prints the line.  Everything else runs with
+``--full``:
+
+* before timing, the run checks its decomposition: the engine with the same
+  process grid and K runs a small domain and is compared with the serial NumPy
+  reference (``check_max_diff``, must be 0 — the engine is bitwise); a
+  mismatch exits non-zero;
+* after timing, the timed field is compared bitwise with a single-sweep
+  replay (``timed_check_*``; a mismatch exits 6);
+* then every other BASELINE quantity above (the extras).
 
 Launch (driver contract):
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -172,6 +182,53 @@ def timed_check(env, eng, sweeps, init, seed, prefix="timed_check"):
     return {f"{prefix}_max_diff": mx, f"{prefix}_mismatches": bad,
             f"{prefix}_path": f"{sweeps} single sweeps + blocking 1-wide exchange ({kind}), bitwise on the device",
             f"{prefix}_s": round(time.perf_counter() - t0, 3)}
+
+
+DUMP_FULL_BYTES = 32 << 20   # a field up to this size is written whole
+DUMP_SAMPLES = 1 << 21       # else this many points (values + indices: 32 MiB)
+DUMP_SEED = 20261019         # of the sample's points, not of the field
+
+
+def dump_outputs(env, eng, out_dir):
+    """--dump-outputs: the field the timed run left (warm-up + timed sweeps
+    of the initial field: what a caller of the engine reads back with
+    ``interior()``), fp64, written by rank 0.  A global field of at most 32 MiB
+    goes out whole as ``u.npy`` (ny x nx); of a larger one a fixed sample:
+    ``u_sample.npy`` holds the values at 2^21 distinct global lattice points
+    drawn once from a seeded generator (the same points for every process
+    grid), ``u_sample_index.npy`` their flat indices gy * nx + gx (as fp64,
+    exact below 2^53), ascending."""
+    ny_g, nx_g = eng.ny_g, eng.nx_g
+    points = ny_g * nx_g
+    whole = points * 8 <= DUMP_FULL_BYTES
+    if whole:
+        idx = np.arange(points, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(points, size=DUMP_SAMPLES, replace=False))
+    eng.synchronize()
+    loc = eng.interior()
+    gy, gx = np.divmod(idx, nx_g)
+    mine = ((gy >= eng.off_y) & (gy < eng.off_y + eng.ny) & (gx >= eng.off_x) & (gx < eng.off_x + eng.nx))
+    part = (np.nonzero(mine)[0], loc[gy[mine] - eng.off_y, gx[mine] - eng.off_x])
+    del loc
+    if env.world_size > 1:
+        parts = [None] * env.world_size
+        torch.distributed.all_gather_object(parts, part, group=env.host_group)
+    else:
+        parts = [part]
+    if env.rank != 0:
+        return
+    vals = np.full(idx.shape, np.nan)
+    for pos, v in parts:
+        vals[pos] = v
+    if np.isnan(vals).any():
+        raise RuntimeError("--dump-outputs: the ranks' shares do not cover every dumped point")
+    os.makedirs(out_dir, exist_ok=True)
+    if whole:
+        np.save(os.path.join(out_dir, "u.npy"), vals.reshape(ny_g, nx_g))
+    else:
+        np.save(os.path.join(out_dir, "u_sample.npy"), vals)
+        np.save(os.path.join(out_dir, "u_sample_index.npy"), idx.astype(np.float64))
 
 
 def check_engine(env, dims, tsteps, graph, init="analytic", seed=0, transport="auto"):
@@ -824,11 +881,17 @@ def main(argv=None):
                          "max(100, 4 x --steps) on the CPU backend)")
     ap.add_argument("--small-size", type=int, default=8192,
                     help="second stencil domain (BASELINE single-GPU config 8192^2; 0 = skip)")
-    ap.add_argument("--skip-extras", action="store_true", help="headline stencil only")
-    ap.add_argument("--skip-check", action="store_true", help="skip the small-domain correctness gate")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the small-domain correctness gate before timing, the check of "
+                         "the timed runs, and every other BASELINE quantity (the extras); off by default")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the field they left to DIR as .npy (fp64; a fixed "
+                         "seeded sample of a field larger than 32 MiB)")
+    ap.add_argument("--skip-extras", action="store_true", help="--full: headline stencil and its checks only")
+    ap.add_argument("--skip-check", action="store_true", help="--full: skip the small-domain correctness gate")
     ap.add_argument("--no-timed-check", action="store_true",
-                    help="skip the check of the timed runs (their final fields against a single-sweep replay, "
-                         "bitwise on the device; a mismatch exits 6)")
+                    help="--full: skip the check of the timed runs (their final fields against a single-sweep "
+                         "replay, bitwise on the device; a mismatch exits 6)")
     ap.add_argument("--ref-n-local", type=int, default=1024,
                     help="reference halo benchmark (N>1): n_local_deriv (mpi_stencil2d_gt default 1024)")
     ap.add_argument("--ref-n-other", type=int, default=512 * 1024,
@@ -855,6 +918,9 @@ def main(argv=None):
     ap.add_argument("--probe-kinds", type=str, default="", help=argparse.SUPPRESS)
     argv = sys.argv[1:] if argv is None else list(argv)
     args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, report
+        args.skip_check = args.no_timed_check = args.skip_extras = True
     # read by the engine library when its first entry point arms the watchdog
     os.environ.setdefault("GMT_TIMEOUT", str(args.timeout))
 
@@ -909,6 +975,10 @@ def main(argv=None):
     # over s_memrealtime; min over ranks): a run's MLUPS against its clock
     extras["timed_pass_sclk_mhz"] = info["clock"]["sclk_mhz"]
     extras["timed_pass_clock_samples"] = info["clock"]["samples"]
+    if args.dump_outputs:
+        # before any extra: the halo latency extra advances the field
+        mark(env, "dump of the timed run's field")
+        dump_outputs(env, solver, args.dump_outputs)
     if not args.no_timed_check:
         # before any extra: the halo latency and residual extras advance the field
         mark(env, "check of the timed run")

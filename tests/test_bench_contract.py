@@ -13,6 +13,8 @@ from conftest import free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
         "scaling", "vs_baseline", "dtype", "data", "config"}
+# the correctness gate, the check of the timed run and the extras run with --full
+BENCH = ["bench.py", "--full"]
 
 
 def _run(cmd, timeout=600, rc=0, **extra_env):
@@ -54,13 +56,77 @@ def _baseline_keys(rec, small):
 
 
 def test_bench_single_process_native_engine_cpu():
-    rec = _run([sys.executable, "bench.py", "--device", "cpu", "--size", "256", "--steps", "20",
+    rec = _run([sys.executable, *BENCH, "--device", "cpu", "--size", "256", "--steps", "20",
                 "--warmup", "5", "--daxpy-n", "20000", "--small-size", "96"])
     _check(rec, 1, 20, 5)
     assert rec["config"]["engine"] == "native"
     _baseline_keys(rec, 96)
     # N = 1: the halo latency is a labelled 1-rank periodic RCCL self-exchange
     assert "self-exchange" in rec["halo_exchange_kind"]
+
+
+def _serial(size, sweeps, seed):
+    sys.path.insert(0, ROOT)
+    from gpu_mpi_tests_amd.engine import serial_jacobi
+
+    return serial_jacobi(size, size, sweeps, init="random", seed=seed)
+
+
+def test_bench_plain_run_is_the_headline_only_cpu(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps and the line — no
+    gate, no replay of the timed run, no extras — and --dump-outputs writes
+    the field the timed run left: the initial field after warm-up + timed
+    sweeps, bitwise the serial NumPy reference, the same from run to run."""
+    import numpy as np
+
+    out = []
+    for d in ("a", "b"):
+        rec = _run([sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--size", "200", "--steps", "7",
+                    "--warmup", "2", "--seed", "11", "--dump-outputs", str(tmp_path / d)])
+        _check(rec, 1, 7, 2, points=200 * 200)
+        assert rec["ms_per_step"] > 0 and rec["config"]["pass_plan"]
+        moved = [k for k in rec if k.startswith(("check_", "timed_check", "daxpy", "halo_", "stencil_", "ref_halo",
+                                                  "residual"))]
+        assert not moved, moved
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["u.npy"]
+        out.append(np.load(tmp_path / d / "u.npy"))
+    assert out[0].dtype == np.float64 and out[0].shape == (200, 200)
+    assert np.array_equal(out[0], out[1])
+    assert np.array_equal(out[0], _serial(200, 9, 11))
+
+
+def test_bench_dump_outputs_two_ranks_full_cpu(tmp_path):
+    """--dump-outputs at N = 2 gathers the ranks' shares, and with --full the
+    dump is still the timed run's field (taken before the extras advance it)."""
+    import numpy as np
+
+    rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), *BENCH, "--gpus", "2",
+                "--device", "cpu", "--size", "200", "--steps", "7", "--warmup", "2", "--seed", "11",
+                "--daxpy-n", "20000", "--ref-n-local", "32", "--ref-n-other", "300", "--ref-iters", "4",
+                "--small-size", "0", "--dump-outputs", str(tmp_path)])
+    _check(rec, 2, 7, 2, points=200 * 200)
+    assert rec["timed_check_mismatches"] == 0 and rec["halo_exchange_us"] > 0
+    assert np.array_equal(np.load(tmp_path / "u.npy"), _serial(200, 9, 11))
+
+
+def test_bench_dump_outputs_samples_a_large_field_cpu(tmp_path):
+    """A field above 32 MiB is dumped as a fixed seeded sample: 2^21 distinct
+    points, their flat global indices beside the values, 32 MiB in all."""
+    import numpy as np
+
+    n = 2100  # 2100^2 fp64 = 33.6 MiB
+    _run([sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--size", str(n), "--steps", "2",
+          "--warmup", "1", "--no-calibrate", "--dump-outputs", str(tmp_path)])
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["u_sample.npy", "u_sample_index.npy"]
+    v, i = np.load(tmp_path / "u_sample.npy"), np.load(tmp_path / "u_sample_index.npy")
+    assert v.dtype == np.float64 and i.dtype == np.float64 and v.shape == i.shape == (1 << 21,)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    idx = i.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n * n
+    import bench
+    assert np.array_equal(idx, np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n * n, 1 << 21, replace=False)))
+    assert np.array_equal(v, _serial(n, 3, 20261017).ravel()[idx])
 
 
 @pytest.mark.parametrize("transport", ["rccl", "ipc"])
@@ -70,7 +136,7 @@ def test_bench_two_ranks_torchrun_cpu(transport):
     oversubscribed GPU ranks use."""
     port = str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "256", "--steps", "3", "--warmup", "1",
                 "--daxpy-n", "20000", "--ref-n-local", "32", "--ref-n-other", "300",
                 "--ref-iters", "4", "--small-size", "96"], GMT_TRANSPORT=transport)
@@ -99,7 +165,7 @@ def test_bench_eight_ranks_driver_shape_cpu():
     BASELINE names is timed too, and every BASELINE key is in the one line."""
     port = str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "8",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "8",
                 "--device", "cpu", "--size", "512", "--steps", "20", "--warmup", "5",
                 "--daxpy-n", "20000", "--ref-n-local", "32", "--ref-n-other", "300",
                 "--ref-iters", "4", "--small-size", "128"], GMT_TRANSPORT="rccl")
@@ -114,7 +180,7 @@ def test_bench_two_ranks_weak_scaling_cpu():
     """--scaling weak: size x size per rank, the global domain grows with N."""
     port = str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "128", "--steps", "13", "--warmup", "1",
                 "--scaling", "weak", "--skip-extras"])
     _check(rec, 2, 13, 1, scaling="weak", points=2 * 128 * 128)
@@ -126,10 +192,10 @@ def test_bench_overlap_autotune_keeps_the_solution():
     restores the initial field: the residual after K steps is the 1-rank one."""
     common = ["--device", "cpu", "--size", "192", "--steps", "17", "--warmup", "2",
               "--daxpy-n", "2000", "--ref-n-local", "16", "--ref-n-other", "64", "--ref-iters", "2"]
-    one = _run([sys.executable, "bench.py", *common])
+    one = _run([sys.executable, *BENCH, *common])
     port = str(free_port())
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2", *common])
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2", *common])
     tuned = two["config"]["overlap_tuning"]
     assert tuned and tuned["overlap_s"] > 0 and tuned["serial_s"] > 0
     assert abs(two["residual_l2"] - one["residual_l2"]) <= 1e-12 * max(1.0, one["residual_l2"])
@@ -144,7 +210,7 @@ def test_bench_ipc_peer_hang_fails_the_job_cpu():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1",
                GMT_TRANSPORT="ipc", GMT_INJECT_HANG="1:2", GMT_WAIT_TIMEOUT_MS="500")
     p = subprocess.run(["timeout", "-k", "5", "120", sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, "bench.py",
+                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, *BENCH,
                         "--gpus", "2", "--device", "cpu", "--size", "128", "--steps", "6", "--warmup", "1",
                         "--skip-extras"], capture_output=True, text=True, timeout=150, cwd=ROOT, env=env)
     assert p.returncode != 0, p.stdout + p.stderr
@@ -163,7 +229,7 @@ def test_bench_rccl_peer_hang_watchdog_cpu():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1",
                GMT_TRANSPORT="rccl", GMT_INJECT_HANG="1:2", GMT_TIMEOUT="4")
     p = subprocess.run(["timeout", "-k", "5", "150", sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, "bench.py",
+                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, *BENCH,
                         "--gpus", "2", "--device", "cpu", "--size", "128", "--steps", "6", "--warmup", "1",
                         "--skip-extras"], capture_output=True, text=True, timeout=180, cwd=ROOT, env=env)
     assert p.returncode != 0, p.stdout + p.stderr
@@ -200,7 +266,7 @@ def test_bench_transport_probe_cpu():
     job runs on the faster one."""
     port, pport = str(free_port()), str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "600", "--steps", "3", "--warmup", "1", "--skip-extras",
                 "--transport-probe", "on", "--probe-port", pport, "--probe-iters", "5", "--probe-passes", "2"])
     cands = rec["transport_candidates"]
@@ -224,7 +290,7 @@ def test_bench_transport_probe_drops_a_crashing_candidate_cpu():
     is untouched, runs on RCCL, and the line names the failure."""
     port, pport = str(free_port()), str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "192", "--steps", "3", "--warmup", "1", "--skip-extras",
                 "--transport-probe", "on", "--probe-port", pport, "--probe-iters", "5", "--probe-timeout", "20"],
                GMT_PROBE_CRASH="1:ipc")
@@ -241,7 +307,7 @@ def test_bench_probe_drops_rccl_every_extra_on_ipc_cpu():
     was dropped ("next round" item 3)."""
     port, pport = str(free_port()), str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "600", "--steps", "3", "--warmup", "1",
                 "--daxpy-n", "20000", "--ref-n-local", "32", "--ref-n-other", "300", "--ref-iters", "4",
                 "--small-size", "96", "--transport-probe", "on", "--probe-port", pport, "--probe-iters", "5",
@@ -263,7 +329,7 @@ def test_bench_extra_hang_keeps_the_headline_cpu():
     EXTRA_HANG_EXIT), which torchrun turns into a failed job."""
     port = str(free_port())
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "2",
+                "--master-addr", "127.0.0.1", "--master-port", port, *BENCH, "--gpus", "2",
                 "--device", "cpu", "--size", "192", "--steps", "3", "--warmup", "1",
                 "--daxpy-n", "20000", "--ref-n-local", "32", "--ref-n-other", "300", "--ref-iters", "4",
                 "--small-size", "0"], timeout=300, rc=-1, GMT_TRANSPORT="rccl", GMT_TIMEOUT="6",
@@ -277,7 +343,7 @@ def test_bench_extra_hang_keeps_the_headline_cpu():
 def test_bench_extra_exception_is_recorded_cpu():
     """An extra that raises is a field of the line, not an exit: a DAXPY of
     an impossible size fails alone and the job still reports."""
-    rec = _run([sys.executable, "bench.py", "--device", "cpu", "--size", "128", "--steps", "4",
+    rec = _run([sys.executable, *BENCH, "--device", "cpu", "--size", "128", "--steps", "4",
                 "--warmup", "1", "--daxpy-n", "-5", "--small-size", "0"])
     _check(rec, 1, 4, 1, points=128 * 128)
     assert "daxpy_error" in rec and "daxpy_all-reduce_error" in rec, sorted(rec)
@@ -287,7 +353,7 @@ def test_bench_extra_exception_is_recorded_cpu():
 def test_bench_extra_hang_exit_status_single_process_cpu():
     """N = 1 (no launcher in between): a hung extra exits with bench.py's
     EXTRA_HANG_EXIT (5) after printing the headline line."""
-    rec = _run([sys.executable, "bench.py", "--device", "cpu", "--size", "128", "--steps", "4", "--warmup", "1",
+    rec = _run([sys.executable, *BENCH, "--device", "cpu", "--size", "128", "--steps", "4", "--warmup", "1",
                 "--daxpy-n", "20000", "--small-size", "0"], timeout=120, rc=5, GMT_TIMEOUT="4",
                GMT_BENCH_HANG="0:daxpy all-reduce")
     assert rec["timed_check_mismatches"] == 0 and "daxpy all-reduce" in rec["watchdog"]
@@ -301,7 +367,7 @@ def test_bench_timed_check_catches_a_corrupt_face_cpu(ranks):
     and the single-sweep replay differs, so the job exits non-zero with the
     mismatch in the line (no small-domain gate: --skip-check; table-planned
     fused passes: --no-calibrate)."""
-    args = ["bench.py", "--gpus", str(ranks), "--device", "cpu", "--size", "600", "--steps", "20",
+    args = [*BENCH, "--gpus", str(ranks), "--device", "cpu", "--size", "600", "--steps", "20",
             "--warmup", "5", "--skip-check", "--no-calibrate", "--skip-extras"]
     if ranks > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
@@ -349,7 +415,7 @@ def test_bench_push_stalled_neighbour_stops_the_passes_cpu():
                GMT_INJECT_HANG="1:10", GMT_WAIT_TIMEOUT_MS="2000")
     t0 = time.time()
     p = subprocess.run(["timeout", "-k", "5", "200", sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, "bench.py",
+                        "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port, *BENCH,
                         "--gpus", "2", "--device", "cpu", "--size", "600", "--steps", "800", "--warmup", "1",
                         "--skip-extras", "--skip-check", "--no-calibrate", "--transport", "push"],
                        capture_output=True, text=True, timeout=230, cwd=ROOT, env=env)

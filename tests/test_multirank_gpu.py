@@ -34,7 +34,7 @@ def _torchrun(n, args, timeout, **env):
     port = str(free_port())
     cmd = ["timeout", "-k", "10", str(timeout), sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), *args]
     e = dict(os.environ, OMP_NUM_THREADS="1", **env)
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout + 30, cwd=ROOT, env=e)
 
