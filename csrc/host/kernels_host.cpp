@@ -54,6 +54,14 @@ int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const double* c, do
   return 0;
 }
 
+// one loop per entry point: no kernel to pick
+int gmt_stencil5_2d_path(int, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_jacobi5_path(int64_t, const double*, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+
 int gmt_copy2d_batched(int n_desc, const gmt_copy2d_desc* d, int elem_bytes, void*) {
   if (n_desc < 0 || n_desc > GMT_MAX_COPY2D || (elem_bytes != 4 && elem_bytes != 8)) return 1;
   for (int k = 0; k < n_desc; ++k) {

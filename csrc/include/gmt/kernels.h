@@ -37,6 +37,15 @@ int gmt_stencil5_1d(int64_t n_out, const double* coef5, double scale,
 int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
                     double scale, const double* in, int64_t ld_in, double* out,
                     int64_t ld_out, void* stream);
+/* Which kernel a launcher picks (tests assert the path a case ran): the
+ * one-element-per-lane fallback, the pair-per-thread kernels (stencil5_pt,
+ * jacobi5_pt), the dim-1 register-window walk, the dim-1 LDS-DMA pipeline.
+ * The CPU backend has no kernels to pick from and answers GMT_PATH_NONE. */
+enum { GMT_PATH_NONE = 0, GMT_PATH_SCALAR = 1, GMT_PATH_PT = 2, GMT_PATH_D1_WIN = 3, GMT_PATH_D1_DMA = 4 };
+/* the kernel gmt_stencil5_2d would launch for these arguments (no launch);
+   *seg_rows (may be NULL) gets the rows per segment of the dim-1 kernels, 0 otherwise */
+int gmt_stencil5_2d_path(int dim, int64_t nx_out, int64_t ny_out, const double* in, int64_t ld_in,
+                         const double* out, int64_t ld_out, int64_t* seg_rows);
 
 /* ---- K6/K7/K8: batched strided 2-D copy (halo pack / unpack, fused L+R).
  *      Each descriptor copies `height` rows of `width` elements of
@@ -134,6 +143,8 @@ int64_t gmt_jacobi_resid_workspace(int64_t nx, int64_t ny);
 int gmt_jacobi5(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u,
                 double* un, int64_t ld, const double* f, int64_t ldf, double c0,
                 double c1, double* resid_partial, void* stream);
+/* GMT_PATH_PT or GMT_PATH_SCALAR for gmt_jacobi5 with these arguments */
+int gmt_jacobi5_path(int64_t x0, const double* u, const double* un, int64_t ld, const double* f, int64_t ldf);
 /* Same sweep for a list of rectangles in one launch (the boundary "frame" of
  * an overlapped step: up to 4 strips).  rect = {x0, nx, y0, ny}. */
 int gmt_jacobi5_rects(int n_rect, const int64_t* rects, const double* u, double* un,

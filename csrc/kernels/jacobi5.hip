@@ -160,7 +160,20 @@ static void reduce_partials(const double* partial, int64_t nb, double* out, hipS
   sum_chunks<<<grid_1d(used), kBlock, 0, s>>>(partial, nb, chunk, l2);
   sum_partials<<<1, kBlock, 0, s>>>(l2, used, out);
 }
+// The one dispatch decision of gmt_jacobi5 (and the answer of
+// gmt_jacobi5_path): pairs per thread need 16-B aligned rows and an even
+// first column.
+static int jacobi5_path(int64_t x0, const double* u, const double* un, int64_t ld, const double* f, int64_t ldf) {
+  const bool vec_ok = aligned16(u) && aligned16(un) && (ld % 2 == 0) && (x0 % 2 == 0) &&
+                      (!f || (aligned16(f) && ldf % 2 == 0));
+  return vec_ok ? GMT_PATH_PT : GMT_PATH_SCALAR;
+}
 }  // namespace gmt
+
+extern "C" int gmt_jacobi5_path(int64_t x0, const double* u, const double* un, int64_t ld, const double* f,
+                                int64_t ldf) {
+  return gmt::jacobi5_path(x0, u, un, ld, f, ldf);
+}
 
 extern "C" int gmt_jacobi5(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u,
                            double* un, int64_t ld, const double* f, int64_t ldf, double c0,
@@ -173,8 +186,7 @@ extern "C" int gmt_jacobi5(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const
   }
   const bool has_f = f != nullptr;
   const bool want_r = resid != nullptr;
-  const bool vec_ok = aligned16(u) && aligned16(un) && (ld % 2 == 0) && (x0 % 2 == 0) &&
-                      (!has_f || (aligned16(f) && ldf % 2 == 0));
+  const bool vec_ok = jacobi5_path(x0, u, un, ld, f, ldf) == GMT_PATH_PT;
   double* partial = want_r ? resid + 1 : nullptr;
   int64_t nb;
   if (vec_ok) {

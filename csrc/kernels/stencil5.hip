@@ -117,7 +117,41 @@ int launch_d1(int64_t nx, int64_t ny_out, const gmt::Coef5& cf, double scale, co
   return static_cast<int>(hipGetLastError());
 }
 
+// The one dispatch decision of gmt_stencil5_2d (and the answer of
+// gmt_stencil5_2d_path): the kernel for these arguments and, for the dim-1
+// kernels, the output rows per segment.
+struct Plan5 {
+  int path;
+  int64_t L;
+};
+
+Plan5 plan5(int dim, int64_t nx_out, int64_t ny_out, const double* in, int64_t ld_in, const double* out,
+            int64_t ld_out) {
+  if (nx_out <= 0 || ny_out <= 0 || (dim != 0 && dim != 1)) return {GMT_PATH_NONE, 0};
+  const bool vec_ok = gmt::aligned16(in) && gmt::aligned16(out) && (ld_in % 2 == 0) && (ld_out % 2 == 0);
+  if (!vec_ok) return {GMT_PATH_SCALAR, 0};
+  if (dim == 1 && nx_out % 2 == 0) return {GMT_PATH_D1_WIN, std::min<int64_t>(256, ny_out)};
+  if (dim == 1) {
+    // segment rows: the 32-bit buffer offsets must reach (L + 4 + P + U) rows
+    // of the wider pitch; 128 rows amortise the 4-row input halo to 3 %
+    const int64_t ld = ld_in > ld_out ? ld_in : ld_out;
+    const int64_t lmax = (int64_t(1) << 31) / (ld * 8) - 4 - gmt::d1::kP - gmt::d1::kU;
+    const int64_t L = std::min<int64_t>(std::min<int64_t>(128, ny_out), lmax);
+    if (L >= 8) return {GMT_PATH_D1_DMA, L};
+  }
+  // one output pair per thread (dim 0: the default; dim 1: rows too long for
+  // the DMA pipeline's 32-bit offsets, or fewer than 8 of them at an odd width)
+  return {GMT_PATH_PT, 0};
+}
+
 }  // namespace
+
+extern "C" int gmt_stencil5_2d_path(int dim, int64_t nx_out, int64_t ny_out, const double* in, int64_t ld_in,
+                                    const double* out, int64_t ld_out, int64_t* seg_rows) {
+  const Plan5 p = plan5(dim, nx_out, ny_out, in, ld_in, out, ld_out);
+  if (seg_rows) *seg_rows = p.L;
+  return p.path;
+}
 
 extern "C" int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
                                double scale, const double* in, int64_t ld_in, double* out,
@@ -127,43 +161,36 @@ extern "C" int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const do
   if (dim != 0 && dim != 1) return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const Coef5 cf = make_coef(coef5);
-  const bool vec_ok = aligned16(in) && aligned16(out) && (ld_in % 2 == 0) && (ld_out % 2 == 0);
-  if (dim == 1 && vec_ok && nx_out % 2 == 0) {
-    constexpr int kNWw = 16, kPw = 4;
-    const int64_t L = std::min<int64_t>(256, ny_out);
-    const int64_t ng = (nx_out + 128 * kNWw - 1) / (128 * kNWw), nseg = (ny_out + L - 1) / L;
-    d1::Args c{};
-    for (int k = 0; k < 5; ++k) c.c[k] = cf.c[k] * scale;
-    d1::stencil5_d1_win<kNWw, kPw><<<grid_1d(ng * nseg), kNWw * kWave, 0, s>>>(nx_out, ny_out, ld_in, ld_out, L,
-                                                                               ng, c, in, out);
-    GMT_RET_LAUNCH();
-  }
-  if (dim == 1 && vec_ok) {
-    // segment rows: the 32-bit buffer offsets must reach (L + 4 + P + U) rows
-    // of the wider pitch; 128 rows amortise the 4-row input halo to 3 %
-    const int64_t ld = ld_in > ld_out ? ld_in : ld_out;
-    const int64_t lmax = (int64_t(1) << 31) / (ld * 8) - 4 - d1::kP - d1::kU;
-    const int64_t L = std::min<int64_t>(std::min<int64_t>(128, ny_out), lmax);
-    if (L >= 8) {
-      if (nx_out % 2) return launch_d1<1, true>(nx_out, ny_out, cf, scale, in, ld_in, out, ld_out, L, s);
-      return launch_d1<1, false>(nx_out, ny_out, cf, scale, in, ld_in, out, ld_out, L, s);
+  const Plan5 p = plan5(dim, nx_out, ny_out, in, ld_in, out, ld_out);
+  switch (p.path) {
+    case GMT_PATH_D1_WIN: {
+      constexpr int kNWw = 16, kPw = 4;
+      const int64_t L = p.L;
+      const int64_t ng = (nx_out + 128 * kNWw - 1) / (128 * kNWw), nseg = (ny_out + L - 1) / L;
+      d1::Args c{};
+      for (int k = 0; k < 5; ++k) c.c[k] = cf.c[k] * scale;
+      d1::stencil5_d1_win<kNWw, kPw><<<grid_1d(ng * nseg), kNWw * kWave, 0, s>>>(nx_out, ny_out, ld_in, ld_out, L,
+                                                                                 ng, c, in, out);
+      break;
     }
-  }
-  if (vec_ok) {
-    // one output pair per thread (dim 0: the default; dim 1: rows too long for
-    // the DMA pipeline's 32-bit offsets)
-    const int64_t nbx = (nx_out + 2 * kWave - 1) / (2 * kWave);
-    const int64_t nb = nbx * ((ny_out + kBlock / kWave - 1) / (kBlock / kWave));
-    if (dim == 0)
-      stencil5_pt<0><<<grid_1d(nb), kBlock, 0, s>>>(nx_out, ny_out, cf, scale, in, ld_in, out,
-                                                    ld_out, nbx, nb);
-    else
-      stencil5_pt<1><<<grid_1d(nb), kBlock, 0, s>>>(nx_out, ny_out, cf, scale, in, ld_in, out,
-                                                    ld_out, nbx, nb);
-  } else {
-    const int64_t nb = (nx_out * ny_out + kBlock - 1) / kBlock;
-    stencil5_scalar<<<grid_1d(nb), kBlock, 0, s>>>(dim, nx_out, ny_out, cf, scale, in, ld_in,
-                                                   out, ld_out);
+    case GMT_PATH_D1_DMA:  // odd widths only: even ones take the window walk
+      return launch_d1<1, true>(nx_out, ny_out, cf, scale, in, ld_in, out, ld_out, p.L, s);
+    case GMT_PATH_PT: {
+      const int64_t nbx = (nx_out + 2 * kWave - 1) / (2 * kWave);
+      const int64_t nb = nbx * ((ny_out + kBlock / kWave - 1) / (kBlock / kWave));
+      if (dim == 0)
+        stencil5_pt<0><<<grid_1d(nb), kBlock, 0, s>>>(nx_out, ny_out, cf, scale, in, ld_in, out,
+                                                      ld_out, nbx, nb);
+      else
+        stencil5_pt<1><<<grid_1d(nb), kBlock, 0, s>>>(nx_out, ny_out, cf, scale, in, ld_in, out,
+                                                      ld_out, nbx, nb);
+      break;
+    }
+    default: {  // GMT_PATH_SCALAR
+      const int64_t nb = (nx_out * ny_out + kBlock - 1) / kBlock;
+      stencil5_scalar<<<grid_1d(nb), kBlock, 0, s>>>(dim, nx_out, ny_out, cf, scale, in, ld_in,
+                                                     out, ld_out);
+    }
   }
   GMT_RET_LAUNCH();
 }

@@ -15,7 +15,13 @@ from .kernels import (  # noqa: F401
     diff_sq,
     xcd_of_workgroups,
     fill_poly,
+    PATH_D1_DMA,
+    PATH_D1_WIN,
+    PATH_NONE,
+    PATH_PT,
+    PATH_SCALAR,
     jacobi5,
+    jacobi5_path,
     jacobi5_rects,
     jacobi5xk,
     jacobi5tb,
@@ -23,6 +29,7 @@ from .kernels import (  # noqa: F401
     tb_supported,
     stencil5_1d,
     stencil5_2d,
+    stencil5_2d_path,
     sum_axis,
     vsum,
 )

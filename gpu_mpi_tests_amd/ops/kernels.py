@@ -106,6 +106,32 @@ def stencil5_2d(inp: torch.Tensor, dim: int, out: torch.Tensor | None = None,
     return out
 
 
+# gmt/kernels.h GMT_PATH_*: the kernel a launcher picks
+PATH_NONE, PATH_SCALAR, PATH_PT, PATH_D1_WIN, PATH_D1_DMA = range(5)
+
+
+def stencil5_2d_path(inp: torch.Tensor, dim: int, out: torch.Tensor) -> tuple[int, int]:
+    """The kernel :func:`stencil5_2d` would launch for these device tensors
+    (gmt_stencil5_2d_path, no launch): ``(PATH_*, rows per segment)``; the
+    rows are 0 for the kernels that do not walk segments."""
+    _check2d(inp, "stencil5_2d_path.inp")
+    _check2d(out, "stencil5_2d_path.out")
+    ny_out, nx_out = out.shape
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_stencil5_2d_path(int(dim), nx_out, ny_out, inp.data_ptr(), inp.stride(0),
+                                              out.data_ptr(), out.stride(0),
+                                              ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def jacobi5_path(u: torch.Tensor, un: torch.Tensor, region: tuple[int, int, int, int],
+                 f: torch.Tensor | None = None) -> int:
+    """The kernel :func:`jacobi5` would launch (gmt_jacobi5_path): PATH_PT or PATH_SCALAR."""
+    return int(_native.lib().gmt_jacobi5_path(int(region[0]), u.data_ptr(), un.data_ptr(), u.stride(0),
+                                              f.data_ptr() if f is not None else 0,
+                                              f.stride(0) if f is not None else 0))
+
+
 # ------------------------------------------------------- halo pack / unpack
 def copy2d_batched(pairs: Sequence[tuple[torch.Tensor, torch.Tensor]], max_wgs: int = 0) -> None:
     """Copy each ``src`` 2-D view into ``dst`` (same shape) in ONE launch.  K6/K7/K8.

@@ -65,18 +65,33 @@ def test_stencil5_1d(n):
 @pytest.mark.parametrize("dim", [0, 1])
 @pytest.mark.parametrize("ny,nx", [(1, 9), (7, 13), (33, 1030), (130, 516), (64, 2049)])
 def test_stencil5_2d(dim, ny, nx):
+    """Contiguous fields: the pitch is the width, so an odd width (dim 0: an
+    odd nx + 4) means unaligned rows and the one-element-per-lane fallback;
+    the padded views of test_kernel_paths_gpu.py reach the other kernels."""
     z = _rand(ny + (4 if dim == 1 else 0), nx + (4 if dim == 0 else 0), seed=6)
-    out = ops.stencil5_2d(z, dim, scale=2.0)
+    out = torch.empty(ny, nx, dtype=torch.float64, device=DEV)
+    if nx % 2:
+        path = (ops.PATH_SCALAR, 0)
+    else:
+        path = (ops.PATH_PT, 0) if dim == 0 else (ops.PATH_D1_WIN, ny)
+    assert ops.stencil5_2d_path(z, dim, out) == path
+    assert ops.stencil5_2d(z, dim, out=out, scale=2.0) is out
     exp = ref.stencil5_2d(z.cpu(), dim, 2.0).to(DEV)
     torch.testing.assert_close(out, exp, rtol=1e-13, atol=1e-13)
 
 
 @pytest.mark.parametrize("ny,nx", [(1, 1), (1, 130), (5, 255), (8, 257), (127, 300), (129, 1031), (300, 640)])
-def test_stencil5_dim1_dma_pipeline(ny, nx):
-    """dim 1 through the LDS-DMA pipeline (stencil5.hip d1): segment tails,
-    partial strips, odd widths (8-B edge stores), taps across segments."""
+def test_stencil5_dim1_contiguous_fields(ny, nx):
+    """dim 1 on contiguous fields: even widths take the register-window walk
+    (one column group; segment tails, taps across the 256-row segments), odd
+    widths have an odd pitch and take the one-element-per-lane fallback.  The
+    LDS-DMA pipeline (odd width, even pitch) and the wider window cases are in
+    test_kernel_paths_gpu.py."""
     z = _rand(ny + 4, nx, seed=16)
-    out = ops.stencil5_2d(z, 1, scale=3.0)
+    out = torch.empty(ny, nx, dtype=torch.float64, device=DEV)
+    path = (ops.PATH_SCALAR, 0) if nx % 2 else (ops.PATH_D1_WIN, min(256, ny))
+    assert ops.stencil5_2d_path(z, 1, out) == path
+    ops.stencil5_2d(z, 1, out=out, scale=3.0)
     exp = ref.stencil5_2d(z.cpu(), 1, 3.0).to(DEV)
     torch.testing.assert_close(out, exp, rtol=1e-13, atol=1e-13)
 
@@ -98,6 +113,8 @@ def test_stencil5_2d_strided_views(dim):
     inp = big[3:3 + 40 + (4 if dim == 1 else 0), 2:2 + 300 + (4 if dim == 0 else 0)]
     outbig = torch.zeros(60, 800, dtype=torch.float64, device=DEV)
     out = outbig[5:45, 10:310]
+    # even pitches, even offsets, an even width: the vector kernels
+    assert ops.stencil5_2d_path(inp, dim, out) == ((ops.PATH_PT, 0) if dim == 0 else (ops.PATH_D1_WIN, 40))
     ops.stencil5_2d(inp, dim, out=out, scale=1.5)
     exp = ref.stencil5_2d(inp.cpu(), dim, 1.5).to(DEV)
     torch.testing.assert_close(out, exp, rtol=1e-13, atol=1e-13)
