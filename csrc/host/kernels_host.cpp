@@ -382,6 +382,11 @@ int64_t gmt_jacobi5tb_group_cols(int sweeps, int wg_waves) {
   return static_cast<int64_t>(nw) * gmt::tb::tb_strip_out(sweeps);
 }
 
+// the GPU kernel's shared hand-off group geometry (gmt/tb_geom.h)
+int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8]) {
+  return out && gmt_jacobi5tb_supported(sweeps) && gmt::tb::sh_geom(sweeps, strips, out) ? 0 : 1;
+}
+
 // in-order CPU streams: the signal was raised before this call runs
 int gmt_signal_wait(const uint64_t* signal, uint64_t* seen, unsigned* err, void*) {
   if (!signal || !seen || !err) return 1;

@@ -261,6 +261,13 @@ int gmt_jacobi5tb(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, con
 int64_t gmt_jacobi5tb_group_cols(int sweeps, int wg_waves);
 int gmt_jacobi5tb_plan(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, const int64_t* dom,
                        int halo_mask, int64_t ld, int64_t nrows, int64_t info[6]);
+/* Column geometry of the shared hand-off group kernel for `sweeps` and
+ * `strips` (2 or 4) per group: out = {GOUT output columns of a group, ML
+ * columns from the group's first window to its first output column, NL levels
+ * per stage, O first stage-1 window's offset, S0 / S1 stage-0 / stage-1 window
+ * spacing, kJW / kJE lane slots of the two one-column Dirichlet keep bodies}.
+ * Non-zero when no group kernel exists for (sweeps, strips). */
+int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8]);
 
 /* One-workgroup kernel on `stream`: waits until *signal > *seen (a
  * gmt_tb_opts completion signal), then advances *seen by one — a stream

@@ -11,6 +11,8 @@
 // lane over four stages, is in git history: profiles/r04_wide.md.)
 #pragma once
 
+#include <cstdint>
+
 namespace gmt {
 namespace tb {
 
@@ -31,6 +33,38 @@ constexpr int tb_default_strips(int K) { return tb_stages(K) == 1 ? 4 : 1; }
 // column masks took 8 SGPRs, K = 6 since the push body is chosen per wave)
 // and K = 14; the engine plans around them
 constexpr bool tb_push_built(int K) { return (K < 6 || K > 10) && K != 14; }
+
+// Shared hand-off groups (csrc/kernels/jacobi5tb.hpp Sh<K, NW>): NW adjacent
+// two-stage strips whose stage-1 waves read 256-column windows of one shared
+// level-K/2 row.  A group kernel exists for two or four strips of a two-stage
+// K whose stages hold an even number of levels (K = 12, 16, 20).
+constexpr int sh_nl(int K) { return K / 2; }                   // levels per stage
+constexpr bool sh_ok(int K, int NW = 4) { return tb_stages(K) == 2 && sh_nl(K) % 2 == 0 && (NW == 2 || NW == 4); }
+constexpr int sh_s0(int K) { return 256 - 2 * sh_nl(K); }      // stage-0 window spacing
+constexpr int sh_o(int K) { return (sh_nl(K) + 3) / 4 * 4; }   // first stage-1 window, from the group's
+constexpr int sh_s1(int K, int NW) {                           // stage-1 window spacing
+  return (sh_s0(K) * (NW - 1) - sh_nl(K) - sh_o(K)) / (NW - 1) / 4 * 4;
+}
+constexpr int sh_gout(int K, int NW) { return sh_s1(K, NW) * (NW - 1) + 256 - 2 * sh_nl(K); }  // output columns of a group
+constexpr int sh_ml(int K) { return sh_o(K) + sh_nl(K); }      // group window start -> output start
+// column slot (0..3 of a lane) of the W / E ghost column in the first / last
+// strip's windows of a pass whose rect is the interior
+constexpr int sh_jw(int K) { return (sh_ml(K) - 1) % 4; }
+constexpr int sh_je(int K, int NW) { return (sh_gout(K, NW) + sh_ml(K)) % 4; }
+// {GOUT, ML, NL, O, S0, S1, kJW, kJE} (gmt_jacobi5tb_shared_geom); false when
+// no group kernel exists for (K, NW)
+constexpr bool sh_geom(int K, int NW, std::int64_t out[8]) {
+  if (!sh_ok(K, NW)) return false;
+  out[0] = sh_gout(K, NW);
+  out[1] = sh_ml(K);
+  out[2] = sh_nl(K);
+  out[3] = sh_o(K);
+  out[4] = sh_s0(K);
+  out[5] = sh_s1(K, NW);
+  out[6] = sh_jw(K);
+  out[7] = sh_je(K, NW);
+  return true;
+}
 
 }  // namespace tb
 }  // namespace gmt

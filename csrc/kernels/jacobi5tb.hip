@@ -168,6 +168,11 @@ extern "C" int64_t gmt_jacobi5tb_group_cols(int sweeps, int wg_waves) {
   return static_cast<int64_t>(nw) * tb_strip_out(sweeps);
 }
 
+extern "C" int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8]) {
+  if (!out || !gmt_jacobi5tb_supported(sweeps) || !sh_geom(sweeps, strips, out)) return static_cast<int>(hipErrorInvalidValue);
+  return 0;
+}
+
 extern "C" int gmt_jacobi5tb_plan(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, const int64_t* dom,
                                   int halo_mask, int64_t ld, int64_t nrows, int64_t info[6]) {
   if (!info) return static_cast<int>(hipErrorInvalidValue);

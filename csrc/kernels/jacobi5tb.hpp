@@ -89,18 +89,19 @@ __host__ __device__ constexpr int64_t strip_lds() {
 template <int K, int NW_ = 4>
 struct Sh {
   static constexpr int NW = NW_;                           // strips per workgroup (2 or 4)
-  static constexpr int NL = K / 2;                         // levels per stage
+  // (the arithmetic is gmt/tb_geom.h's, which gmt_jacobi5tb_shared_geom reports)
+  static constexpr int NL = sh_nl(K);                      // levels per stage
   static constexpr bool kOk = tb_stages(K) == 2 && NL % 2 == 0;
-  static constexpr int S0 = 256 - 2 * NL;                  // stage-0 window spacing
-  static constexpr int O = (NL + 3) / 4 * 4;               // first stage-1 window, from the group's
-  static constexpr int S1 = (S0 * (NW - 1) - NL - O) / (NW - 1) / 4 * 4;  // stage-1 spacing
-  static constexpr int GOUT = S1 * (NW - 1) + 256 - 2 * NL;  // output columns of a group
-  static constexpr int ML = O + NL;                        // group window start -> output start
+  static constexpr int S0 = sh_s0(K);                      // stage-0 window spacing
+  static constexpr int O = sh_o(K);                        // first stage-1 window, from the group's
+  static constexpr int S1 = sh_s1(K, NW);                  // stage-1 spacing
+  static constexpr int GOUT = sh_gout(K, NW);              // output columns of a group
+  static constexpr int ML = sh_ml(K);                      // group window start -> output start
   // column slot of the W / E ghost column in the first / last strip's
   // windows of a pass whose rect is the interior (both stages alike: O, S0
   // and S1 are multiples of 4)
-  static constexpr int kJW = (ML - 1) % 4;
-  static constexpr int kJE = (GOUT + ML) % 4;
+  static constexpr int kJW = sh_jw(K);
+  static constexpr int kJE = sh_je(K, NW);
   static constexpr int kCols = S0 * (NW - 1) + 256;        // input columns of a group
   static constexpr int NG = kCols <= 512 ? 128 : 256;      // 4-column groups of a shared row
   static constexpr uint32_t QS = NG * 16;                  // pair-plane stride (bytes)

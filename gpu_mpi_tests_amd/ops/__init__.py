@@ -26,6 +26,7 @@ from .kernels import (  # noqa: F401
     jacobi5xk,
     jacobi5tb,
     jacobi5tb_plan,
+    jacobi5tb_shared_geom,
     tb_supported,
     stencil5_1d,
     stencil5_2d,

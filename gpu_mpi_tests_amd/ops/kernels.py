@@ -440,6 +440,17 @@ def jacobi5tb_plan(k: int, rects: Sequence[tuple[int, int, int, int]], dom: tupl
     return dict(zip(keys, (int(v) for v in info)))
 
 
+def jacobi5tb_shared_geom(k: int, strips: int = 4) -> dict:
+    """Column geometry of the shared hand-off group kernel for ``k`` sweeps and
+    ``strips`` (2 or 4) per group (gmt_jacobi5tb_shared_geom, the kernel's own
+    constants): GOUT, ML, NL, O, S0, S1, kJW, kJE.  Raises where no group
+    kernel exists."""
+    out = (ctypes.c_int64 * 8)()
+    if _native.lib().gmt_jacobi5tb_shared_geom(int(k), int(strips), ctypes.cast(out, ctypes.c_void_p)) != 0:
+        raise ValueError(f"jacobi5tb_shared_geom: no shared group kernel for {k} sweeps, {strips} strips")
+    return dict(zip(("GOUT", "ML", "NL", "O", "S0", "S1", "kJW", "kJE"), (int(v) for v in out)))
+
+
 def jacobi5xk(k: int, u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],
               dom: tuple[int, int, int, int], halo_mask: int = 0) -> None:
     """``k`` fused Laplace sweeps with the default launch: :func:`jacobi5tb`."""

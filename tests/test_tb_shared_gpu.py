@@ -15,9 +15,24 @@ from gpu_mpi_tests_amd.ops import reference as ref
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-# output columns of one group (Sh<K, 4>::GOUT, Sh<K, 2>::GOUT)
-GOUT = {12: 952, 16: 936, 20: 920}
-GOUT2 = {12: 472, 16: 464, 20: 448}
+# output columns of one group (Sh<K, 4>::GOUT, Sh<K, 2>::GOUT): the documented values
+DOC_GOUT = {4: {12: 952, 16: 936, 20: 920}, 2: {12: 472, 16: 464, 20: 448}}
+
+
+class _Gout:
+    """GOUT[k] from the kernel's own geometry (ops.jacobi5tb_shared_geom),
+    asserted to be the documented value."""
+
+    def __init__(self, strips):
+        self.strips = strips
+
+    def __getitem__(self, k):
+        g = ops.jacobi5tb_shared_geom(k, self.strips)["GOUT"]
+        assert g == DOC_GOUT[self.strips][k], (k, self.strips, g)
+        return g
+
+
+GOUT, GOUT2 = _Gout(4), _Gout(2)
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -84,6 +99,17 @@ def test_shared_multi_round(ny, nx, seg_rows):
     a = _run(k, u, dom, 0, 1, cpu=False, seg_rows=seg_rows)
     b = _run(k, u, dom, 0, -1, cpu=False)
     assert torch.equal(a, b), int((a != b).sum())
+
+
+def test_shared_geometry_documented():
+    for strips, doc in DOC_GOUT.items():
+        for k, gout in doc.items():
+            g = ops.jacobi5tb_shared_geom(k, strips)
+            assert g["GOUT"] == gout and g["NL"] == k // 2
+            assert g["kJW"] == (g["ML"] - 1) % 4 and g["kJE"] == (g["GOUT"] + g["ML"]) % 4
+    for k, strips in [(10, 4), (14, 4), (18, 2), (13, 4), (20, 3), (20, 8), (22, 4)]:
+        with pytest.raises(ValueError):
+            ops.jacobi5tb_shared_geom(k, strips)
 
 
 def test_shared_not_for_narrow_or_push():
