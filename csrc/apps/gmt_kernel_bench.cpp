@@ -128,6 +128,7 @@ int main(int argc, char** argv) {
     // --tb-k=12,14,16 --tb-nw=1,2,4,8 --tb-seg=0 --jacobi-n=32768
     // --tb-mask=0 (Dirichlet everywhere: rule workgroups at the edges)
     // --jacobi-ny=8192 --jacobi-nx=16384 (default: n x n)
+    // --tb-shared=N (gmt_tb_opts.shared of the plain and the --tb-push=1 pass)
     const int64_t n = cli.geti("jacobi-n", 32768);
     // --jacobi-ny / --jacobi-nx: a rectangular domain (a strong-scaling share)
     const int64_t ny = cli.geti("jacobi-ny", n), nx = cli.geti("jacobi-nx", n);
@@ -144,6 +145,7 @@ int main(int argc, char** argv) {
       return v;
     };
     const int mask = static_cast<int>(cli.geti("tb-mask", 0));
+    const int shared = static_cast<int>(cli.geti("tb-shared", 0));
     for (int K : list("tb-k", "12,14,16")) {
       const int64_t g = K, xk = ((g + 7) / 8) * 8;
       const int64_t ld2 = ((xk + nx + g + 63) / 64) * 64, rows = ny + 2 * g;
@@ -155,6 +157,7 @@ int main(int argc, char** argv) {
         for (int P : list("tb-p", "3"))
           for (int seg : list("tb-seg", "0")) {
             gmt_tb_opts o{K, nw, seg, 0};
+            o.shared = shared;
             const double ms = time_ms(s, iters, [&] {
               GMT_CHECK("tb", gmt_jacobi5tb(&o, 1, rect, rect, mask, a.data(), b.data(), ld2, rows, s));
             });
@@ -173,6 +176,12 @@ int main(int argc, char** argv) {
               const double* tgt[8] = {bb + dy, bb - dy, bb + dx, bb - dx, bb + dy + dx, bb + dy - dx, bb - dy + dx, bb - dy - dx};
               for (int d = 0; d < 8; ++d) op.push[d] = tgt[d];  // GMT_PUSH_S, N, W, E, SW, SE, NW, NE
               op.push_w = g;  // even K: the faces fill the g-wide ghost ring
+              // --tb-shared=N with a push pass in shared hand-off groups: the
+              // per-strip push pass (shared = -1) joins the alternation, so one
+              // run gives push-group, plain group and per-strip push
+              gmt_tb_opts ops = op;
+              ops.shared = -1;
+              const int push_path = gmt_jacobi5tb_shared_path(&op, 1, rect, mask);
               for (int rep = 0; rep < 2; ++rep) {
                 const double mp = time_ms(s, iters, [&] {
                   GMT_CHECK("tb push", gmt_jacobi5tb(&op, 1, rect, rect, mask, a.data(), b.data(), ld2, rows, s));
@@ -180,14 +189,29 @@ int main(int argc, char** argv) {
                 const double m0 = time_ms(s, iters, [&] {
                   GMT_CHECK("tb", gmt_jacobi5tb(&o, 1, rect, rect, mask, a.data(), b.data(), ld2, rows, s));
                 });
-                std::printf("%-10s    %-30s push %.4f ms  plain %.4f ms  ratio %.4f\n", "", tag, mp, m0, mp / m0);
+                if (push_path > 0) {
+                  const double m1 = time_ms(s, iters, [&] {
+                    GMT_CHECK("tb push", gmt_jacobi5tb(&ops, 1, rect, rect, mask, a.data(), b.data(), ld2, rows, s));
+                  });
+                  std::printf("%-10s    %-30s push-group%d %.4f ms  plain %.4f ms  per-strip push %.4f ms  "
+                              "ratio to plain %.4f  to per-strip push %.4f\n",
+                              "", tag, push_path, mp, m0, m1, mp / m0, mp / m1);
+                } else {
+                  std::printf("%-10s    %-30s push %.4f ms  plain %.4f ms  ratio %.4f\n", "", tag, mp, m0, mp / m0);
+                }
               }
+              int64_t pp[6] = {};
+              GMT_CHECK("plan", gmt_jacobi5tb_plan(&op, 1, rect, rect, mask, ld2, rows, pp));
+              std::printf("%-10s    %-30s push plan: shared path %d (wgs %lld resident %lld threads %lld seg %lld x %lld vgpr %lld)\n",
+                          "", tag, push_path, (long long)pp[0], (long long)pp[1], (long long)pp[2], (long long)pp[3],
+                          (long long)pp[4], (long long)pp[5]);
             }
             int64_t pi[6] = {};
             GMT_CHECK("plan", gmt_jacobi5tb_plan(&o, 1, rect, rect, mask, ld2, rows, pi));
-            std::printf("%-10s    %-30s %9.1f MLUPS  (wgs %lld resident %lld threads %lld seg %lld x %lld vgpr %lld)\n",
-                        "", tag, K * double(ny) * nx / (ms * 1e-3) / 1e6, (long long)pi[0], (long long)pi[1],
-                        (long long)pi[2], (long long)pi[3], (long long)pi[4], (long long)pi[5]);
+            std::printf("%-10s    %-30s %9.1f MLUPS  (shared path %d wgs %lld resident %lld threads %lld seg %lld x %lld vgpr %lld)\n",
+                        "", tag, K * double(ny) * nx / (ms * 1e-3) / 1e6, gmt_jacobi5tb_shared_path(&o, 1, rect, mask),
+                        (long long)pi[0], (long long)pi[1], (long long)pi[2], (long long)pi[3], (long long)pi[4],
+                        (long long)pi[5]);
           }
     }
   }

@@ -22,6 +22,10 @@
 //   --push                  inline halo exchange of the fused passes (JacobiConfig::push: the
 //                           pass stores its faces into the neighbours' ghost cells; ipc or
 //                           a single rank)
+//   --shared=N              gmt_tb_opts.shared of the fused passes, --push ones included
+//                           (JacobiConfig::tb_shared: -1 no shared hand-off groups, 0 default,
+//                           1 / 4 groups of four strips, 2 of two; a push pass takes groups
+//                           only when asked for here)
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -115,6 +119,12 @@ int main(int argc, char** argv) {
   c.wg_waves = static_cast<int>(cli.geti("wg-strips", 0));
   c.seg_rows = static_cast<int>(cli.geti("seg-rows", 0));
   c.push = cli.flag("push");
+  c.tb_shared = static_cast<int>(cli.geti("shared", 0));
+  if (c.tb_shared != -1 && c.tb_shared != 0 && c.tb_shared != 1 && c.tb_shared != 2 && c.tb_shared != 4) {
+    if (rank == 0) std::printf("ERROR: --shared=%d is not one of -1, 0, 1, 2, 4\n", c.tb_shared);
+    std::fflush(stdout);
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
   // with one rank and no periodic wrap there is nothing to exchange; with a
   // periodic wrap a single rank exchanges with itself
   comm::Kind kind = comm::parse_kind(cli.get("transport", "auto"));
@@ -125,12 +135,14 @@ int main(int argc, char** argv) {
   bool graph = false, overlap = false, band = false, push = false;
   size_t hbytes = 0, hmsgs = 0;
   int64_t lnx = 0, lny = 0;
+  int sh_strips = 0;
   {
     JacobiSolver solver(*tr, c);
     graph = solver.graph_active();
     overlap = solver.overlap_active();
     band = solver.band_first();
     push = solver.push_active();
+    if (c.tblock && c.tsteps > 1) sh_strips = solver.tb_shared_strips(solver.tsteps());
     hbytes = solver.bytes_per_exchange();
     hmsgs = solver.messages();
     lnx = solver.nx();
@@ -196,6 +208,9 @@ int main(int argc, char** argv) {
     std::printf("transport = %s overlap=%d%s graph=%d periodic=%d tblock=%d backend=%s\n", tr->name(),
                 overlap, band ? " (band-first)" : (push ? " (inline halo)" : ""), graph, c.periodic, c.tblock,
                 gmt_rt_backend_name());
+    if (c.tb_shared != 0)
+      std::printf("shared    = %d (rank 0: %d strips per shared hand-off group, 0 = per-strip launch)\n", c.tb_shared,
+                  sh_strips);
     std::printf("steps     = %d (warmup %d)\n", n_iter, n_warmup);
     std::printf("TIME step : %0.6f ms\n", t_step * 1e3);
     std::printf("MLUPS     : %0.1f (per GPU %0.1f, %0.1f GB/s per GPU at 16 B/pt)\n", mlups,
@@ -208,7 +223,7 @@ int main(int argc, char** argv) {
     JsonRecord j;
     j.add("app", "mpi_jacobi2d").add("ranks", world).add("py", c.py).add("px", c.px)
         .add("ny", (long long)c.ny_global).add("nx", (long long)c.nx_global).add("transport", tr->name())
-        .add("overlap", overlap).add("band_first", band).add("push", push).add("graph", graph).add("tblock", c.tblock).add("steps", n_iter).add("ms_per_step", t_step * 1e3)
+        .add("overlap", overlap).add("band_first", band).add("push", push).add("shared_strips", sh_strips).add("graph", graph).add("tblock", c.tblock).add("steps", n_iter).add("ms_per_step", t_step * 1e3)
         .add("MLUPS", mlups).add("halo_us", halo_us).add("halo_bytes", hbytes).add("residual", resid)
         .add("check_max_diff", max_diff);
     j.append_to(cli.get("json", ""));

@@ -134,7 +134,8 @@ void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank,
   if (opts) o = *opts;
   if (o.tsteps < 0 || o.tsteps > GMT_TB_MAX_SWEEPS || o.overlap < 0 || o.overlap > 2 || o.wg_waves < 0 ||
       o.wg_waves > 8 || o.seg_rows < 0 || o.exact < -1 || o.exact > 1 || o.init < 0 || o.init > 1 ||
-      o.calibrate < 0 || o.calibrate > 1 || o.seed < 0 || o.seed >= (int64_t(1) << 53) || o.push < 0 || o.push > 1)
+      o.calibrate < 0 || o.calibrate > 1 || o.seed < 0 || o.seed >= (int64_t(1) << 53) || o.push < 0 || o.push > 1 ||
+      !(o.shared == -1 || o.shared == 0 || o.shared == 1 || o.shared == 2 || o.shared == 4))
     return nullptr;
   auto* h = new Handle();
   h->t = gmt::engine_transport(rank, world, transport, ccl_id);
@@ -161,6 +162,7 @@ void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank,
   c.seed = static_cast<uint64_t>(o.seed);
   c.calibrate = o.calibrate != 0;
   c.push = o.push != 0;
+  c.tb_shared = o.shared;
   h->py = py;
   h->px = px;
   h->s = std::make_unique<gmt::JacobiSolver>(*h->t, c);
@@ -216,6 +218,7 @@ int gmt_engine_jacobi_info(void* p, int64_t* out) {
 int gmt_engine_jacobi_tb_info(void* p, int K, int64_t* out) {
   return static_cast<Handle*>(p)->s->tb_launch_info(K, out);
 }
+int gmt_engine_jacobi_tb_shared(void* p, int K) { return static_cast<Handle*>(p)->s->tb_shared_strips(K); }
 int gmt_engine_jacobi_plan(void* p, int steps, int* out, int max) {
   const std::vector<int> plan = static_cast<Handle*>(p)->s->plan_passes(steps);
   for (int i = 0; i < static_cast<int>(plan.size()) && i < max; ++i) out[i] = plan[i];

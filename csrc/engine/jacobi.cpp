@@ -383,6 +383,7 @@ void JacobiSolver::xk_launch(int K, int n, const int64_t* rects, int parity, int
   gmt_tb_opts o{K,   cfg_.wg_waves, cfg_.seg_rows, exact_ ? 1 : 0, sig_rects, sig ? count : nullptr,
                 sig ? sig_.data() + 1 : nullptr, sig_rows, st == sb_ && sb_ ? comm_cus_ : 0, sig_cols};
   o.clock = clk_.data();
+  o.shared = cfg_.tb_shared;
   GMT_CHECK("jacobi tb", gmt_jacobi5tb(&o, n, rects, dom, mask, u, un, ld_, ny_ + 2 * g_, st ? st : s_));
 }
 
@@ -601,6 +602,7 @@ void JacobiSolver::push_block(int parity, int K) {
   o.push_w = g_;
   o.stop = push_stop_.data();
   o.clock = clk_.data();
+  o.shared = cfg_.tb_shared;
   GMT_CHECK("jacobi tb (inline halo)", gmt_jacobi5tb(&o, 1, dom, dom, halo_mask(), buf_[parity].data(),
                                                      buf_[parity ^ 1].data(), ld_, ny_ + 2 * g_, s_));
   if (push_mask_) {
@@ -623,7 +625,19 @@ int JacobiSolver::tb_launch_info(int K, int64_t out[6]) const {
     for (int d = 0; d < 8; ++d) o.push[d] = push_base_[parity_][d];
     o.push_w = g_;
   }
+  o.shared = cfg_.tb_shared;
   return gmt_jacobi5tb_plan(&o, 1, dom, dom, halo_mask(), ld_, ny_ + 2 * g_, out);
+}
+
+int JacobiSolver::tb_shared_strips(int K) const {
+  const int64_t dom[4] = {xo_, nx_, yo_, ny_};
+  gmt_tb_opts o{};
+  o.sweeps = K;
+  o.wg_waves = cfg_.wg_waves;
+  o.seg_rows = cfg_.seg_rows;
+  o.push_w = push_on_ ? g_ : 0;
+  o.shared = cfg_.tb_shared;
+  return gmt_jacobi5tb_shared_path(&o, 1, dom, halo_mask());
 }
 
 bool JacobiSolver::band_mode(int K) const {

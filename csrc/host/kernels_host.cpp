@@ -387,6 +387,11 @@ int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8]) {
   return out && gmt_jacobi5tb_supported(sweeps) && gmt::tb::sh_geom(sweeps, strips, out) ? 0 : 1;
 }
 
+// no group kernels on the CPU: gmt_tb_opts.shared is accepted and ignored,
+// for inline-halo passes too
+int gmt_jacobi5tb_push_shared_supported(int, int) { return 0; }
+int gmt_jacobi5tb_shared_path(const gmt_tb_opts*, int, const int64_t*, int) { return 0; }
+
 // in-order CPU streams: the signal was raised before this call runs
 int gmt_signal_wait(const uint64_t* signal, uint64_t* seen, unsigned* err, void*) {
   if (!signal || !seen || !err) return 1;

@@ -45,6 +45,8 @@ typedef struct gmt_engine_opts {
                     planner uses those costs instead of the built-in table */
   int64_t seed;
   int push;     /* 1: inline halo exchange of the fused passes (JacobiConfig::push) */
+  int shared;   /* gmt_tb_opts.shared of the fused passes, inline-halo ones included
+                   (JacobiConfig::tb_shared): -1, 0 (default), 1, 2 or 4 */
 } gmt_engine_opts;
 /* id: 128 bytes (RCCL unique id / control id) or NULL (local); NULL on invalid options */
 void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank, int world,
@@ -64,6 +66,9 @@ int gmt_engine_jacobi_plan(void* h, int steps, int* out, int max);
 /* The launch of the rank's one-rect K-sweep pass (gmt_jacobi5tb_plan's
  * info[6]); returns its error code. */
 int gmt_engine_jacobi_tb_info(void* h, int K, int64_t* out);
+/* Strips per shared hand-off group (2 or 4) of that pass, 0 for a per-strip
+ * launch (gmt_jacobi5tb_shared_path). */
+int gmt_engine_jacobi_tb_shared(void* h, int K);
 /* Launch one pass of every pass type run(steps) will use, then restore the
  * initial field (first-launch costs stay out of a timed run). */
 int gmt_engine_jacobi_prepare(void* h, int steps);

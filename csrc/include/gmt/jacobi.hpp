@@ -84,6 +84,12 @@ struct JacobiConfig {
   // rank; off (the transport's exchange as before) when the share is too
   // small for the kernel's push rules.
   bool push = false;
+  // gmt_tb_opts.shared of every fused pass, inline-halo ones included: -1 no
+  // shared hand-off groups, 0 the kernel's default (an inline-halo pass then
+  // runs the per-strip kernel), 1 / 4 four-strip groups, 2 two-strip groups.
+  // Each rank decides its own launch: a share narrower than a group keeps
+  // the per-strip kernel.
+  int tb_shared = 0;
 };
 
 class JacobiSolver {
@@ -128,6 +134,8 @@ class JacobiSolver {
   // {workgroups, resident workgroups, threads per workgroup, segment rows,
   // segments, VGPRs}.  Returns its error code (0: ok).
   int tb_launch_info(int K, int64_t out[6]) const;
+  // strips per shared hand-off group of that pass (gmt_jacobi5tb_shared_path), 0: per-strip
+  int tb_shared_strips(int K) const;
 
   int64_t nx() const { return nx_; }
   int64_t ny() const { return ny_; }

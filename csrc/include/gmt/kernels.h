@@ -215,9 +215,11 @@ typedef struct gmt_tb_opts {
      [x1 - push_w, x1) to E, their w x w intersections to the diagonals, of
      the one rect (which must be `dom`).  Needs: push_w even and <= 64;
      two strips or more when both W and E are pushed (a strip pushes one
-     x face); the segment planner keeps every segment clear of one of the
-     S / N faces; no completion signal options; rects of even width or
-     wider than a strip (no odd-edge stores). */
+     x face; a shared hand-off group always has two windows or more); the
+     segment planner keeps every segment clear of one of the S / N faces;
+     no completion signal options; rects of even width or wider than a
+     strip (no odd-edge stores).  A push pass runs the per-strip kernel
+     unless shared hand-off groups are asked for explicitly (`shared`). */
   const double* push[8];
   int push_w;
   /* Inline-halo passes only (push_w > 0): a device word (NULL = none) that a
@@ -234,13 +236,19 @@ typedef struct gmt_tb_opts {
   uint64_t* clock;
   /* Shared hand-off groups (csrc/kernels/jacobi5tb.hpp Sh<K>): K = 12, 16,
      20 passes of one rect at least a group wide (920 columns at K = 20),
-     with no push, signals or wg_waves, run as workgroups of four strips
+     with no signals or wg_waves, run as workgroups of four strips
      whose stage-1 waves read windows of one shared hand-off row — 6% fewer
      level updates per output at K = 20.  Bitwise the same field.
      -1 = off, 1 = on (four-strip groups), 2 / 4 = on with groups of that
      many strips (448 / 920 output columns at K = 20), 0 = default: four-
      strip groups where both x sides exchange halos, two-strip groups for
-     other rects of 2^28 points or more (GMT_TB_SHARED=0 / 1 / 2 / 4 forces it). */
+     other rects of 2^28 points or more (GMT_TB_SHARED=0 / 1 / 2 / 4 forces it).
+     An inline-halo pass (push_w > 0) takes groups only when asked for
+     explicitly (shared or GMT_TB_SHARED = 1 / 2 / 4): the first window of
+     the first group then pushes the W face, the last window of the last
+     group the E face.  With 0 (and GMT_TB_SHARED unset), for a rect
+     narrower than a group, or where no push-group kernel is built
+     (gmt_jacobi5tb_push_shared_supported) it runs the per-strip push kernel. */
   int shared;
 } gmt_tb_opts;
 enum { GMT_PUSH_S = 0, GMT_PUSH_N = 1, GMT_PUSH_W = 2, GMT_PUSH_E = 3,
@@ -268,6 +276,15 @@ int gmt_jacobi5tb_plan(const gmt_tb_opts* opts, int n_rect, const int64_t* rects
  * spacing, kJW / kJE lane slots of the two one-column Dirichlet keep bodies}.
  * Non-zero when no group kernel exists for (sweeps, strips). */
 int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8]);
+/* An inline-halo (gmt_tb_opts.push) kernel in shared hand-off groups of
+ * `strips` (2 or 4) strips is built for `sweeps`. */
+int gmt_jacobi5tb_push_shared_supported(int sweeps, int strips);
+/* The strips per shared hand-off group (2 or 4) gmt_jacobi5tb would launch
+ * for these options and rects, or 0 for a per-strip launch: the launcher's own
+ * decision, inline-halo passes included; nothing is launched.  (A workgroup
+ * of 256 threads is a two-strip group or two plain strips: gmt_jacobi5tb_plan
+ * cannot tell them apart.) */
+int gmt_jacobi5tb_shared_path(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, int halo_mask);
 
 /* One-workgroup kernel on `stream`: waits until *signal > *seen (a
  * gmt_tb_opts completion signal), then advances *seen by one — a stream

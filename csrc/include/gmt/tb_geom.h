@@ -66,5 +66,10 @@ constexpr bool sh_geom(int K, int NW, std::int64_t out[8]) {
   return true;
 }
 
+// (K, NW) with an inline-halo (push) group kernel: a K with both a group
+// kernel and a push kernel whose push-group body fits 2 waves per SIMD
+// without scratch or VGPR spills (tests/test_kernel_resources.py)
+constexpr bool tb_push_sh_built(int K, int NW) { return sh_ok(K, NW) && tb_push_built(K); }
+
 }  // namespace tb
 }  // namespace gmt

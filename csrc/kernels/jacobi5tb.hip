@@ -173,6 +173,24 @@ extern "C" int gmt_jacobi5tb_shared_geom(int sweeps, int strips, int64_t out[8])
   return 0;
 }
 
+extern "C" int gmt_jacobi5tb_push_shared_supported(int sweeps, int strips) {
+  return gmt_jacobi5tb_supported(sweeps) && tb_push_sh_built(sweeps, strips);
+}
+
+extern "C" int gmt_jacobi5tb_shared_path(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, int halo_mask) {
+  if (!opts || !rects || n_rect < 0 || n_rect > kMaxRect) return 0;
+  switch (opts->sweeps) {
+    case 12:
+      return sh_launch<12>(*opts, n_rect, rects, halo_mask);
+    case 16:
+      return sh_launch<16>(*opts, n_rect, rects, halo_mask);
+    case 20:
+      return sh_launch<20>(*opts, n_rect, rects, halo_mask);
+    default:
+      return 0;  // no group kernel
+  }
+}
+
 extern "C" int gmt_jacobi5tb_plan(const gmt_tb_opts* opts, int n_rect, const int64_t* rects, const int64_t* dom,
                                   int halo_mask, int64_t ld, int64_t nrows, int64_t info[6]) {
   if (!info) return static_cast<int>(hipErrorInvalidValue);

@@ -1,7 +1,9 @@
 // Temporal-blocking Jacobi kernel and its launch code (see jacobi5tb.hip for
 // the design).  Included by the jacobi5tb_k*.hip translation units, each of
 // which instantiates dispatch_k for a few K: the fully unrolled register
-// pipelines take minutes per K to compile, so they build in parallel.
+// pipelines take minutes per K to compile, so they build in parallel.  The
+// jacobi5tb_ps*.hip units instantiate the inline-halo group launches
+// (push_sh_launch), one (K, strips) each.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -404,7 +406,8 @@ __device__ __forceinline__ void keep_col(dv<NC>& v, double c, uint64_t m) {
 // stored, this (output) wave publishes a row-band arrival (Args::rb_rect).
 // PUSH (inline halo exchange, output stage): bit 0 = this strip holds an x
 // face (W / E columns), bit 1 = this segment holds y-face rows (S / N); both:
-// the corner too.
+// the corner too.  The face stores work from the wave's output range
+// [xs, xe) and its lane columns alone, so an SH window pushes like a strip.
 // SH (shared hand-off group): cf is the wave's own window (stage-dependent),
 // ring + hdelta + 16 lane this lane's group in the shared hand-off ring
 // (stage 0 writes it under the ownership masks hm0 / hm1, stage 1 reads it;
@@ -443,7 +446,7 @@ __device__ __forceinline__ void run_stage(const Args& a, const double* __restric
   const int64_t dx0 = a.dom[0], dx1 = a.dom[0] + a.dom[1];
   const int64_t dy0 = a.dom[2], dy1 = a.dom[2] + a.dom[3];
   using SHG = Sh<K, SH ? SH : 4>;  // (SH: the group's strips, 2 or 4)
-  static_assert(!SH || (SHG::kOk && !EDGE && PUSH == 0 && !UP), "SH: one-rect passes, plain bodies");
+  static_assert(!SH || (SHG::kOk && !EDGE && !UP), "SH: one-rect passes, top-down bodies");
   constexpr uint32_t kQS = SHG::QS, kRowG = SHG::ROWG;
   char* const hsh = ring + 16 * lane + hdelta;
   const int64_t c0 = cf + NC * lane;    // this lane: columns c0 .. c0+NC-1
@@ -607,8 +610,14 @@ __device__ __forceinline__ void run_stage(const Args& a, const double* __restric
   const auto clamp32 = [](int64_t x) {
     return static_cast<int>(x < INT32_MIN ? int64_t{INT32_MIN} : x > INT32_MAX ? int64_t{INT32_MAX} : x);
   };
-  const int tlo = up ? (gn ? INT32_MIN : clamp32(yanchor - dy1 + 1)) : (gs ? INT32_MIN : clamp32(dy0 - yanchor));
-  const int thi = up ? (gs ? INT32_MAX : clamp32(yanchor - dy0 + 1)) : (gn ? INT32_MAX : clamp32(dy1 - yanchor));
+  int tlo = up ? (gn ? INT32_MIN : clamp32(yanchor - dy1 + 1)) : (gs ? INT32_MIN : clamp32(dy0 - yanchor));
+  int thi = up ? (gs ? INT32_MAX : clamp32(yanchor - dy0 + 1)) : (gn ? INT32_MAX : clamp32(dy1 - yanchor));
+  if constexpr (PUSH != 0 && SH != 0) {
+    // wave-uniform: pinned to SGPRs, as keep_cells' scalar compare takes
+    // them (the 64-bit clamps may be evaluated on the VALU)
+    tlo = __builtin_amdgcn_readfirstlane(tlo);
+    thi = __builtin_amdgcn_readfirstlane(thi);
+  }
   // (mod 2^32: t - tlo in [0, span) <=> tlo <= t < thi, for |t| < 2^30)
   const uint32_t span = static_cast<uint32_t>(thi) - static_cast<uint32_t>(tlo);
   auto level = [&](const dv<NC>& up_, const dv<NC>& c, const dv<NC>& dn, int t) -> dv<NC> {
@@ -931,8 +940,12 @@ __device__ __forceinline__ void tb_block(const Args& a, const double* __restrict
   // multiple of 4, left of its first output column: W ghost in slot 3, E
   // ghost 256 - KL right of the last strip's window start, slot 0)
   // (SH only: in the per-strip K = 20 kernel the two extra bodies spilled
-  // 12-14 VGPRs)
-  constexpr bool kColBodies = SH;
+  // 12-14 VGPRs; and not in an inline-halo group kernel: next to the push
+  // bodies the two stage-0 one-column bodies of K = 20 spilled 3 VGPRs each,
+  // 16 B of scratch per lane, for two and four strips, exact and scaled —
+  // its rule waves all take the general keep: the waves of a group run in
+  // step, so one-column stage-1 bodies alone would gain nothing)
+  constexpr bool kColBodies = SH && !PUSH;
   constexpr int kJW = SH ? Sh<K, SH ? SH : 4>::kJW : 3, kJE = SH ? Sh<K, SH ? SH : 4>::kJE : 0;
   if constexpr (kColBodies) {
     const bool ry = (ys - K < a.dom[2] && !(a.mask & 4)) || (ye + K > a.dom[2] + a.dom[3] && !(a.mask & 8));
@@ -946,7 +959,11 @@ __device__ __forceinline__ void tb_block(const Args& a, const double* __restrict
   // one instantiation per (stage, rule path, direction); the direction is
   // bottom-up only for the N row bands
   // the x face this strip pushes (PUSH): the first strip holds the W one,
-  // the last the E one (launch_tb: at least two strips when both are pushed)
+  // the last the E one (launch_tb: at least two strips when both are pushed).
+  // SH: the first window of group 0 and the last window of the last
+  // (shifted) group — S1 >= 212 and 256 - 2 NL >= 236 columns wide, both
+  // wider than the largest face (64); NL and 256 - NL are even, so a face
+  // starts on a column pair of its lanes; NW >= 2 windows: never one wave
   const bool pw = PUSH && (a.push[GMT_PUSH_W] || a.push[GMT_PUSH_SW] || a.push[GMT_PUSH_NW]);
   const bool pe = PUSH && (a.push[GMT_PUSH_E] || a.push[GMT_PUSH_SE] || a.push[GMT_PUSH_NE]);
   const int xd = !PUSH ? -1 : (strip == 0 && pw) ? GMT_PUSH_W : (strip == a.nstrip[k] - 1 && pe) ? GMT_PUSH_E : -1;
@@ -961,9 +978,13 @@ __device__ __forceinline__ void tb_block(const Args& a, const double* __restrict
   const int pm = (xd >= 0 ? 1 : 0) | (py ? 2 : 0);
   using T = std::true_type;
   using F = std::false_type;
-  auto go = [&](auto jc, auto rule_c, auto up_c, int sstep) {
+  // (always_inline: with the unrolled bodies of a push-group kernel — twelve
+  // when it still built the one-column keep ones — the compiler left the
+  // stage-1 dispatch a function of its own, whose calling convention cost
+  // the bodies their registers: 206-224 VGPRs spilled at K = 20)
+  auto go = [&](auto jc, auto rule_c, auto up_c, int sstep) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
-    auto run = [&](auto push_c) {
+    auto run = [&](auto push_c) __attribute__((always_inline)) {
       run_stage<K, j, EXACT, EDGE, decltype(rule_c)::value, decltype(up_c)::value, decltype(push_c)::value, SH>(
           a, u, un, ring, lane, xs, xe, ys, ye, nsteps, sstep, xd, cf, hdelta, hm0, hm1);
     };
@@ -978,7 +999,7 @@ __device__ __forceinline__ void tb_block(const Args& a, const double* __restrict
       run(P0{});
     }
   };
-  auto stage_go = [&](auto jc, int sstep) {
+  auto stage_go = [&](auto jc, int sstep) __attribute__((always_inline)) {
     if constexpr (!SH) {
       if (!PUSH && dir < 0) {  // (no row bands in an inline-halo pass)
         if (rule) go(jc, std::integral_constant<int, 1>{}, T{}, sstep);
@@ -1004,7 +1025,7 @@ __device__ __forceinline__ void tb_block(const Args& a, const double* __restrict
   if constexpr (G == 1) {
     stage_go(std::integral_constant<int, 0>{}, sig_step);
   } else {
-    static_for<0, G>([&](auto Jc) {
+    static_for<0, G>([&](auto Jc) __attribute__((always_inline)) {
       constexpr int j = decltype(Jc)::value;
       if (stage == j) {
         if constexpr (j == 0) {
@@ -1450,7 +1471,7 @@ int launch_tb(const gmt_tb_opts& o, int n_rect, const int64_t* rects, const int6
     const char* e = std::getenv("GMT_TB_COL_KEEP");
     return e ? std::atoi(e) : 1;
   }();
-  a.col_keep = col_keep != 0 && SH;
+  a.col_keep = col_keep != 0 && SH && !PUSH;  // (tb_block: kColBodies)
   if constexpr (!SH && G > 1) {
     // several two-stage strips per workgroup: stage-major waves (all the
     // stage-0 waves first) — 32768^2 with two strips 5.24-5.25M MLUPS
@@ -1476,7 +1497,7 @@ int launch_tb(const gmt_tb_opts& o, int n_rect, const int64_t* rects, const int6
     a.shmap = strip_map != 0 && a.nw > 1;
   }
   if constexpr (SH) {
-    static_assert(Sh<K, SH>::kOk && !EDGE && !PUSH, "SH launches: plain two-stage bodies");
+    static_assert(Sh<K, SH>::kOk && !EDGE, "SH launches: two-stage bodies, no odd-edge stores");
     a.nw = Sh<K, SH>::NW;
     a.sh = 1;
     // stage-major waves: each SIMD then holds one stage-0 and one stage-1
@@ -1509,10 +1530,13 @@ int launch_tb(const gmt_tb_opts& o, int n_rect, const int64_t* rects, const int6
     const auto any = [&](int d0, int d1, int d2) { return o.push[d0] || o.push[d1] || o.push[d2]; };
     push_sides = (any(GMT_PUSH_W, GMT_PUSH_SW, GMT_PUSH_NW) ? 1 : 0) | (any(GMT_PUSH_E, GMT_PUSH_SE, GMT_PUSH_NE) ? 2 : 0) |
                  (any(GMT_PUSH_S, GMT_PUSH_SW, GMT_PUSH_SE) ? 4 : 0) | (any(GMT_PUSH_N, GMT_PUSH_NW, GMT_PUSH_NE) ? 8 : 0);
-    // a strip pushes one x face
-    if (any(GMT_PUSH_W, GMT_PUSH_SW, GMT_PUSH_NW) && any(GMT_PUSH_E, GMT_PUSH_SE, GMT_PUSH_NE) &&
-        (dom[1] + C::WOUT - 1) / C::WOUT < 2)
-      return static_cast<int>(hipErrorInvalidValue);
+    // a strip pushes one x face (an SH group has two windows or more: W and
+    // E always fall to different waves)
+    if constexpr (!SH) {
+      if (any(GMT_PUSH_W, GMT_PUSH_SW, GMT_PUSH_NW) && any(GMT_PUSH_E, GMT_PUSH_SE, GMT_PUSH_NE) &&
+          (dom[1] + C::WOUT - 1) / C::WOUT < 2)
+        return static_cast<int>(hipErrorInvalidValue);
+    }
   }
   using SHG = Sh<K, SH ? SH : 4>;
   constexpr int64_t wout = SH ? SHG::GOUT : C::WOUT;  // SH: a group's columns
@@ -1733,9 +1757,12 @@ namespace gmt {
 namespace tb {
 
 // An SH launch (Sh<K>: stage-1 windows over a shared hand-off row) for a
-// pass of one rect at least a group wide, with no inline halo, completion
-// signals or explicit workgroup shape.  gmt_tb_opts.shared: 1 on, -1 off,
-// 0 the default (GMT_TB_SHARED=1 / 0 forces it on / off).
+// pass of one rect at least a group wide, with no completion signals or
+// explicit workgroup shape.  gmt_tb_opts.shared: 1 on, -1 off, 0 the default
+// (GMT_TB_SHARED=1 / 0 forces it on / off).  An inline-halo pass (push_w > 0)
+// takes groups only when asked for explicitly (shared or GMT_TB_SHARED =
+// 1 / 2 / 4) and a push-group kernel is built (tb_push_sh_built); by default
+// it keeps the per-strip push kernel.
 template <int K>
 int sh_launch(const gmt_tb_opts& o, int n_rect, const int64_t* rects, int mask) {
   if constexpr (!Sh<K>::kOk) {
@@ -1748,7 +1775,8 @@ int sh_launch(const gmt_tb_opts& o, int n_rect, const int64_t* rects, int mask) 
       return e ? std::atoi(e) : -1;
     }();
     if (o.shared < 0 || (o.shared == 0 && env == 0)) return 0;
-    if (o.push_w > 0 || o.wg_waves > 0 || o.signal_rects > 0 || o.signal_rows > 0 || (o.signal_cols & 3)) return 0;
+    if (o.wg_waves > 0 || o.signal_rects > 0 || o.signal_rows > 0 || (o.signal_cols & 3)) return 0;
+    if (o.push_w > 0 && !(o.shared > 0 || (o.shared == 0 && env > 0))) return 0;
     // the default (o.shared == 0, GMT_TB_SHARED unset): four-strip groups
     // for a rect whose x sides both exchange halos (+2-3% on the one-round
     // N = 8 shares, +2% at 32768^2); two-strip groups for a larger rect
@@ -1773,6 +1801,7 @@ int sh_launch(const gmt_tb_opts& o, int n_rect, const int64_t* rects, int mask) 
       else if (area >= (int64_t(1) << 28)) w = 2;
       else return 0;
     }
+    if (o.push_w > 0 && !tb_push_sh_built(K, w)) return 0;
     const int64_t gout = w == 2 ? Sh<K, 2>::GOUT : Sh<K, 4>::GOUT;
     for (int k = 0; k < n_rect; ++k)
       if (rects[4 * k + 1] > 0 && rects[4 * k + 3] > 0 && rects[4 * k + 1] < gout) return 0;
@@ -1780,11 +1809,37 @@ int sh_launch(const gmt_tb_opts& o, int n_rect, const int64_t* rects, int mask) 
   }
 }
 
+// An inline-halo pass in shared hand-off groups of NW strips.  The kernels
+// are instantiated in translation units of their own (jacobi5tb_ps*.hip),
+// which keeps them out of the per-K units' compile time.
+template <int K, int NW>
+int push_sh_launch(const gmt_tb_opts& o, bool exact, int n_rect, const int64_t* rects, const int64_t* dom, int mask,
+                   const double* u, double* un, int64_t ld, int64_t nrows, hipStream_t s, int64_t* info) {
+  if constexpr (tb_push_sh_built(K, NW)) {
+    return exact ? launch_tb<K, true, false, true, NW>(o, n_rect, rects, dom, mask, u, un, ld, nrows, s, info)
+                 : launch_tb<K, false, false, true, NW>(o, n_rect, rects, dom, mask, u, un, ld, nrows, s, info);
+  } else {
+    return static_cast<int>(hipErrorInvalidValue);
+  }
+}
+#define GMT_TB_PUSH_SH(KW, K, NW)                                                                                  \
+  KW template int push_sh_launch<K, NW>(const gmt_tb_opts&, bool, int, const int64_t*, const int64_t*, int,      \
+                                        const double*, double*, int64_t, int64_t, hipStream_t, int64_t*)
+GMT_TB_PUSH_SH(extern, 12, 2);
+GMT_TB_PUSH_SH(extern, 12, 4);
+GMT_TB_PUSH_SH(extern, 16, 2);
+GMT_TB_PUSH_SH(extern, 16, 4);
+GMT_TB_PUSH_SH(extern, 20, 2);
+GMT_TB_PUSH_SH(extern, 20, 4);
+
 template <int K>
 int dispatch_k(const gmt_tb_opts& o, bool exact, int n_rect, const int64_t* rects, const int64_t* dom, int mask,
                const double* u, double* un, int64_t ld, int64_t nrows, hipStream_t s, int64_t* info) {
   if constexpr (Sh<K>::kOk) {
     const int w = sh_launch<K>(o, n_rect, rects, mask);
+    if (o.push_w > 0 && w > 0)  // (sh_launch: a push-group kernel is built for (K, w))
+      return w == 4 ? push_sh_launch<K, 4>(o, exact, n_rect, rects, dom, mask, u, un, ld, nrows, s, info)
+                    : push_sh_launch<K, 2>(o, exact, n_rect, rects, dom, mask, u, un, ld, nrows, s, info);
     if (w == 4)
       return exact ? launch_tb<K, true, false, false, 4>(o, n_rect, rects, dom, mask, u, un, ld, nrows, s, info)
                    : launch_tb<K, false, false, false, 4>(o, n_rect, rects, dom, mask, u, un, ld, nrows, s, info);

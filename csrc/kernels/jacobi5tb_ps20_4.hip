@@ -1,0 +1,9 @@
+// Instantiations of the temporal-blocking kernel (jacobi5tb.hpp): the inline-halo
+// (push) pass in shared hand-off groups of 4 strips, K = 20.
+#include "jacobi5tb.hpp"
+
+namespace gmt {
+namespace tb {
+GMT_TB_PUSH_SH(, 20, 4);
+}  // namespace tb
+}  // namespace gmt

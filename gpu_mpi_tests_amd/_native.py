@@ -107,6 +107,8 @@ _SIGS = {
     "gmt_jacobi5tb_plan": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_vp]),
     "gmt_jacobi5tb_group_cols": (c_i64, [c_int, c_int]),
     "gmt_jacobi5tb_shared_geom": (c_int, [c_int, c_int, c_vp]),
+    "gmt_jacobi5tb_push_shared_supported": (c_int, [c_int, c_int]),
+    "gmt_jacobi5tb_shared_path": (c_int, [c_vp, c_int, c_vp, c_int]),
     "gmt_signal_wait": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gmt_stage_copy": (c_int, [c_int, c_vp, c_vp, c_vp, ctypes.c_uint64, c_int, c_vp]),
     "gmt_stage_scatter": (c_int, [c_int, c_vp, c_int, c_vp]),

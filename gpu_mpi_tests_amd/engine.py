@@ -48,7 +48,7 @@ class EngineOpts(ctypes.Structure):
     """gmt_engine_opts (csrc/include/gmt/engine.h)."""
     _fields_ = [(n, ctypes.c_int) for n in
                 ("periodic", "overlap", "graph", "tsteps", "wg_waves", "seg_rows", "exact", "init",
-                 "calibrate")] + [("seed", ctypes.c_int64), ("push", ctypes.c_int)]
+                 "calibrate")] + [("seed", ctypes.c_int64), ("push", ctypes.c_int), ("shared", ctypes.c_int)]
 
 
 class EngineError(RuntimeError):
@@ -98,6 +98,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_info.restype = c_int
     lib.gmt_engine_jacobi_tb_info.argtypes = [vp, c_int, ctypes.POINTER(i64)]
     lib.gmt_engine_jacobi_tb_info.restype = c_int
+    lib.gmt_engine_jacobi_tb_shared.argtypes = [vp, c_int]
+    lib.gmt_engine_jacobi_tb_shared.restype = c_int
     lib.gmt_engine_jacobi_plan.argtypes = [vp, c_int, ctypes.POINTER(c_int), c_int]
     lib.gmt_engine_jacobi_plan.restype = c_int
     lib.gmt_engine_jacobi_prepare.argtypes = [vp, c_int]
@@ -287,12 +289,20 @@ class NativeJacobi:
                  overlap: "bool | str" = True, graph: bool = True,
                  tblock: bool | int = False, wg_waves: int = 0, seg_rows: int = 0, exact: int = -1,
                  transport: str = "auto", init: str = "analytic", seed: int = 0, calibrate: bool = False,
-                 push: bool = False):
+                 push: bool = False, shared: int = 0):
         """push: the fused passes exchange their halo inline (each pass stores
         its output faces straight into the neighbours' ghost cells over IPC
         mappings, then one hand-over launch; gmt/jacobi.hpp JacobiConfig::push).
         Needs the IPC transport when a neighbour is another rank; silently the
-        transport's exchange when the share is too small (``push_active``)."""
+        transport's exchange when the share is too small (``push_active``).
+        shared: gmt_tb_opts.shared of every fused pass, push passes included
+        (JacobiConfig::tb_shared): -1 no shared hand-off groups, 0 the kernel's
+        default (a push pass then runs the per-strip kernel), 1 / 4 groups of
+        four strips, 2 of two.  Each rank decides its own launch
+        (``tb_launch(k)["shared_strips"]``): a share narrower than a group
+        keeps the per-strip kernel."""
+        if shared not in (-1, 0, 1, 2, 4) or isinstance(shared, bool):
+            raise ValueError(f"shared must be -1, 0, 1, 2 or 4, got {shared!r}")
         from .parallel.decomp import choose_dims
 
         self.env = env or gdist.get()
@@ -329,7 +339,8 @@ class NativeJacobi:
         opts = EngineOpts(periodic=int(bool(periodic)), overlap=2 if auto else int(bool(overlap)),
                           graph=int(bool(graph)), tsteps=ks, wg_waves=int(wg_waves),
                           seg_rows=int(seg_rows), exact=int(exact), init=INITS[init],
-                          calibrate=int(bool(calibrate)), seed=int(seed), push=int(bool(push)))
+                          calibrate=int(bool(calibrate)), seed=int(seed), push=int(bool(push)),
+                          shared=int(shared))
         with _StdoutToStderr():
             self.h = self.lib.gmt_engine_jacobi_create(ny, nx, py, px, e.rank, e.world_size, transport,
                                                        cid, ctypes.byref(opts))
@@ -408,21 +419,28 @@ class NativeJacobi:
     def tb_launch(self, k: int) -> dict:
         """The launch shape of this rank's one-rect k-sweep pass
         (gmt_jacobi5tb_plan, nothing launched): workgroups, resident slots,
-        threads per workgroup, segment rows and count, VGPRs; ``shape`` names
-        it — for two-stage strips 128 threads are one strip per workgroup,
-        256 two stage-major strips, 512 a shared hand-off group (default
-        wg_waves) — csrc/kernels/jacobi5tb.hpp launch_tb / sh_launch."""
+        threads per workgroup, segment rows and count, VGPRs;
+        ``shared_strips``: the strips per shared hand-off group (2 or 4), 0
+        for a per-strip launch (gmt_jacobi5tb_shared_path — 256 threads are a
+        two-strip group or two plain strips); ``shape`` names it — for
+        two-stage strips 128 threads are one strip per workgroup, 256 two
+        stage-major strips, 512 four (default wg_waves) —
+        csrc/kernels/jacobi5tb.hpp launch_tb / sh_launch."""
         out = (ctypes.c_int64 * 6)()
         rc = self.lib.gmt_engine_jacobi_tb_info(self.h, int(k), out)
         if rc != 0:
             return {"error": int(rc)}
         keys = ("workgroups", "resident", "threads", "seg_rows", "segments", "vgprs")
         d = dict(zip(keys, (int(v) for v in out)))
+        sh = d["shared_strips"] = int(self.lib.gmt_engine_jacobi_tb_shared(self.h, int(k)))
         if k > 10 and d["threads"] in (128, 256, 512):
-            d["shape"] = {128: "one two-stage strip per workgroup",
-                          256: "two two-stage strips per workgroup, stage-major waves (a shared "
-                               "hand-off pair unless push / GMT_TB_SHARED=0)",
-                          512: "shared hand-off group: four strips, stage-major waves"}[d["threads"]]
+            if sh:
+                d["shape"] = (f"shared hand-off group: {'two' if sh == 2 else 'four'} strips, stage-major waves"
+                              + (", inline halo exchange" if self.push_active else ""))
+            else:
+                d["shape"] = {128: "one two-stage strip per workgroup",
+                              256: "two two-stage strips per workgroup, stage-major waves",
+                              512: "four two-stage strips per workgroup, stage-major waves"}[d["threads"]]
         return d
 
     def clock_reset(self) -> None:

@@ -27,6 +27,8 @@ from .kernels import (  # noqa: F401
     jacobi5tb,
     jacobi5tb_plan,
     jacobi5tb_shared_geom,
+    jacobi5tb_shared_path,
+    tb_push_shared_supported,
     tb_supported,
     stencil5_1d,
     stencil5_2d,

@@ -388,7 +388,9 @@ def jacobi5tb(k: int, u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[i
     "NW" "NE") with ``push_w``: the inline halo exchange (gmt_tb_opts.push) —
     the output's face cells are also stored into each tensor at the same
     coordinates (a tensor with ``un``'s row pitch).  ``shared``: the shared hand-off
-    group launch (gmt_tb_opts.shared: 1 on, -1 off, 0 default = on where it applies)."""
+    group launch (gmt_tb_opts.shared: 1 / 4 on with four-strip groups, 2 with
+    two-strip groups, -1 off, 0 default = on where it applies; a push pass takes
+    groups only when asked for, see :func:`jacobi5tb_shared_path`)."""
     rects = [tuple(int(v) for v in r) for r in rects if r[1] > 0 and r[3] > 0]
     if not tb_supported(k):
         raise ValueError(f"jacobi5tb: {k} sweeps per pass is not built (1..10 or even 12..{TB_MAX_SWEEPS})")
@@ -422,22 +424,56 @@ def jacobi5tb(k: int, u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[i
 
 def jacobi5tb_plan(k: int, rects: Sequence[tuple[int, int, int, int]], dom: tuple[int, int, int, int],
                    halo_mask: int, ld: int, nrows: int, *, wg_waves: int = 0, seg_rows: int = 0,
-                   shared: int = 0) -> dict:
+                   shared: int = 0, push: "dict | None" = None, push_w: int = 0) -> dict:
     """The launch :func:`jacobi5tb` would make (gmt_jacobi5tb_plan), without
     launching: workgroups, resident workgroups, threads per workgroup (512 for
-    a shared hand-off group launch), interior segment rows and count, VGPRs."""
+    a four-strip shared hand-off group launch), interior segment rows and
+    count, VGPRs.  ``push`` / ``push_w``: as in :func:`jacobi5tb` (only which
+    directions are pushed matters: a value may be a tensor or anything true)."""
     L = _native.lib()
     rects = [tuple(int(v) for v in r) for r in rects]
     arr = (ctypes.c_int64 * (4 * len(rects)))(*[v for r in rects for v in r])
     d = (ctypes.c_int64 * 4)(*[int(v) for v in dom])
     o = _native.TbOpts(int(k), int(wg_waves), int(seg_rows), 0)
     o.shared = int(shared)
+    if push:
+        for dirn, t in push.items():
+            if t is not None and t is not False:
+                # (nothing is dereferenced: any aligned non-null address)
+                o.push[_PUSH_DIRS.index(dirn)] = t.data_ptr() if isinstance(t, torch.Tensor) else 8
+        o.push_w = int(push_w)
     info = (ctypes.c_int64 * 6)()
     _native.check(L.gmt_jacobi5tb_plan(ctypes.byref(o), len(rects), ctypes.cast(arr, ctypes.c_void_p),
                                        ctypes.cast(d, ctypes.c_void_p), int(halo_mask), int(ld), int(nrows),
                                        ctypes.cast(info, ctypes.c_void_p)), "gmt_jacobi5tb_plan")
     keys = ("workgroups", "resident", "threads", "seg_rows", "segments", "vgprs")
     return dict(zip(keys, (int(v) for v in info)))
+
+
+_PUSH_DIRS = ("S", "N", "W", "E", "SW", "SE", "NW", "NE")
+
+
+def jacobi5tb_shared_path(k: int, rects: Sequence[tuple[int, int, int, int]], halo_mask: int, *, shared: int = 0,
+                          wg_waves: int = 0, push_w: int = 0) -> int:
+    """Strips per shared hand-off group (2 or 4) that :func:`jacobi5tb` would
+    launch for these arguments, 0 for a per-strip launch
+    (gmt_jacobi5tb_shared_path: the launcher's own decision, nothing is
+    launched).  ``push_w`` > 0: an inline-halo pass, which takes groups only
+    when ``shared`` (or GMT_TB_SHARED) asks for them and a push-group kernel
+    is built (:func:`tb_push_shared_supported`)."""
+    rects = [tuple(int(v) for v in r) for r in rects]
+    arr = (ctypes.c_int64 * max(4, 4 * len(rects)))(*[v for r in rects for v in r])
+    o = _native.TbOpts(int(k), int(wg_waves), 0, 0)
+    o.shared = int(shared)
+    o.push_w = int(push_w)
+    return int(_native.lib().gmt_jacobi5tb_shared_path(ctypes.byref(o), len(rects), ctypes.cast(arr, ctypes.c_void_p),
+                                                       int(halo_mask)))
+
+
+def tb_push_shared_supported(k: int, strips: int) -> bool:
+    """An inline-halo (push) kernel in shared hand-off groups of ``strips``
+    strips is built for ``k`` sweeps (gmt_jacobi5tb_push_shared_supported)."""
+    return bool(_native.lib().gmt_jacobi5tb_push_shared_supported(int(k), int(strips)))
 
 
 def jacobi5tb_shared_geom(k: int, strips: int = 4) -> dict:
