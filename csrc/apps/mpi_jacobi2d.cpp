@@ -132,13 +132,15 @@ int main(int argc, char** argv) {
   auto tr = comm::make_transport(comm::resolve(kind, b), MPI_COMM_WORLD, b);
 
   double t_step = 0, resid = 0, halo_us = 0, max_diff = -1;
-  bool graph = false, overlap = false, band = false, push = false;
+  bool graph = false, overlap = false, band = false, push = false, graph_sweep = false, graph_fused = false;
   size_t hbytes = 0, hmsgs = 0;
   int64_t lnx = 0, lny = 0;
   int sh_strips = 0;
   {
     JacobiSolver solver(*tr, c);
     graph = solver.graph_active();
+    graph_sweep = solver.sweep_graph_active();
+    graph_fused = solver.fused_graph_active();
     overlap = solver.overlap_active();
     band = solver.band_first();
     push = solver.push_active();
@@ -208,6 +210,9 @@ int main(int argc, char** argv) {
     std::printf("transport = %s overlap=%d%s graph=%d periodic=%d tblock=%d backend=%s\n", tr->name(),
                 overlap, band ? " (band-first)" : (push ? " (inline halo)" : ""), graph, c.periodic, c.tblock,
                 gmt_rt_backend_name());
+    // which passes replay from hipGraphs: single sweeps, full fused passes
+    // (inline-halo ones with their hand-over); partial passes are always eager
+    if (c.graph) std::printf("graphs    = sweep:%d fused:%d\n", graph_sweep, graph_fused);
     if (c.tb_shared != 0)
       std::printf("shared    = %d (rank 0: %d strips per shared hand-off group, 0 = per-strip launch)\n", c.tb_shared,
                   sh_strips);
@@ -223,7 +228,7 @@ int main(int argc, char** argv) {
     JsonRecord j;
     j.add("app", "mpi_jacobi2d").add("ranks", world).add("py", c.py).add("px", c.px)
         .add("ny", (long long)c.ny_global).add("nx", (long long)c.nx_global).add("transport", tr->name())
-        .add("overlap", overlap).add("band_first", band).add("push", push).add("shared_strips", sh_strips).add("graph", graph).add("tblock", c.tblock).add("steps", n_iter).add("ms_per_step", t_step * 1e3)
+        .add("overlap", overlap).add("band_first", band).add("push", push).add("shared_strips", sh_strips).add("graph", graph).add("graph_fused", graph_fused).add("tblock", c.tblock).add("steps", n_iter).add("ms_per_step", t_step * 1e3)
         .add("MLUPS", mlups).add("halo_us", halo_us).add("halo_bytes", hbytes).add("residual", resid)
         .add("check_max_diff", max_diff);
     j.append_to(cli.get("json", ""));

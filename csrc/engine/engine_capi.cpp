@@ -215,6 +215,10 @@ int gmt_engine_jacobi_info(void* p, int64_t* out) {
   out[15] = s.push_active();
   return 0;
 }
+int gmt_engine_jacobi_graphs(void* p) {
+  auto& s = *static_cast<Handle*>(p)->s;
+  return (s.sweep_graph_active() ? 1 : 0) | (s.fused_graph_active() ? 2 : 0);
+}
 int gmt_engine_jacobi_tb_info(void* p, int K, int64_t* out) {
   return static_cast<Handle*>(p)->s->tb_launch_info(K, out);
 }

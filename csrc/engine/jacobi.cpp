@@ -525,6 +525,10 @@ void JacobiSolver::setup_push() {
   *push_err_.data() = 0;
   push_stop_ = Buffer<unsigned>(1, GMT_SPACE_DEVICE);
   GMT_CHECK("push stop", gmt_rt_memset_async(push_stop_.data(), 0, push_stop_.bytes(), s_));
+  // the hand-over's epoch lives on the device (gmt_push_sync_dev): a captured
+  // hand-over replays with the epoch of its pass, not of its capture
+  push_ctl_ = Buffer<uint64_t>(2, GMT_SPACE_DEVICE);
+  GMT_CHECK("push epoch", gmt_rt_memset_async(push_ctl_.data(), 0, push_ctl_.bytes(), s_));
   GMT_CHECK("push stop", gmt_rt_stream_synchronize(s_));
   PushWire mine;
   std::memset(&mine, 0, sizeof(mine));
@@ -593,6 +597,25 @@ void JacobiSolver::setup_push() {
 void JacobiSolver::push_block(int parity, int K) {
   if (!fresh_[parity]) exchange_now(parity);
   maybe_corrupt(parity);
+  push_pass(parity, K);
+  if (push_mask_) {
+    fault_point_exchange(t_.rank());  // GMT_INJECT_HANG: the hand-over is this pass's exchange
+    push_handover();
+  }
+  fresh_[parity ^ 1] = true;
+}
+
+// The stream work of one inline-halo block is a plain chain on the compute
+// stream: push_pass, then push_handover.  Every argument of both is fixed per
+// parity (the epoch is a device word), so capture_graphs records exactly
+// these two launches and a replay is the block of whichever pass comes next.
+void JacobiSolver::push_handover() {
+  unsigned* arrivals = reinterpret_cast<unsigned*>(push_ctl_.data() + 1);
+  GMT_CHECK("push hand-over", gmt_push_sync_dev(push_flags_.data(), push_remote_, push_mask_, push_ctl_.data(),
+                                                arrivals, push_err_.data(), push_stop_.data(), s_));
+}
+
+void JacobiSolver::push_pass(int parity, int K) {
   const int64_t dom[4] = {xo_, nx_, yo_, ny_};
   gmt_tb_opts o{};
   o.sweeps = K;
@@ -605,13 +628,6 @@ void JacobiSolver::push_block(int parity, int K) {
   o.shared = cfg_.tb_shared;
   GMT_CHECK("jacobi tb (inline halo)", gmt_jacobi5tb(&o, 1, dom, dom, halo_mask(), buf_[parity].data(),
                                                      buf_[parity ^ 1].data(), ld_, ny_ + 2 * g_, s_));
-  if (push_mask_) {
-    fault_point_exchange(t_.rank());  // GMT_INJECT_HANG: the hand-over is this pass's exchange
-    ++push_epoch_;
-    GMT_CHECK("push hand-over", gmt_push_sync(push_flags_.data(), push_remote_, push_mask_, push_epoch_,
-                                             push_err_.data(), push_stop_.data(), s_));
-  }
-  fresh_[parity ^ 1] = true;
 }
 
 int JacobiSolver::tb_launch_info(int K, int64_t out[6]) const {
@@ -647,7 +663,16 @@ bool JacobiSolver::band_mode(int K) const {
 }
 
 void JacobiSolver::step_block() {
-  if (graph2_[parity_]) {
+  if (graph2_[parity_] && push_on_) {
+    // an inline-halo graph is the pass and its hand-over, captured from a
+    // current halo; the per-pass host hooks of the eager path run here, so
+    // GMT_CORRUPT_PASS and GMT_INJECT_HANG keep counting passes
+    if (!fresh_[parity_]) exchange_now(parity_);
+    maybe_corrupt(parity_);
+    if (push_mask_) fault_point_exchange(t_.rank());
+    GMT_CHECK("graph launch", gmt_rt_graph_launch(graph2_[parity_], s_));
+    fresh_[parity_ ^ 1] = true;
+  } else if (graph2_[parity_]) {
     // a band-first graph starts from a current halo (it was captured so)
     const bool band = band_mode(ks_);
     if (band && !fresh_[parity_]) exchange_now(parity_);
@@ -796,16 +821,25 @@ void JacobiSolver::capture_graphs() {
   GMT_CHECK("sync", gmt_rt_stream_synchronize(cs_));
   const bool saved[2] = {fresh_[0], fresh_[1]};
   for (int p = 0; p < 4; ++p) {
-    if (p >= 2 && (ks_ < 2 || push_on_)) break;  // inline-halo passes carry a per-pass epoch: eager
-    // serial passes capture their exchange, band-first ones start from a
-    // current halo (step_block makes sure of it)
+    if (p >= 2 && ks_ < 2) break;  // no fused passes
+    // serial passes capture their exchange; band-first and inline-halo ones
+    // start from a current halo (step_block makes sure of it)
     fresh_[0] = fresh_[1] = p >= 2 && band_mode(ks_);
     int e = gmt_rt_stream_begin_capture(s_);
     if (e == 0) {
-      if (p < 2)
+      if (p < 2) {
         enqueue_step(p);
-      else
+      } else if (push_on_) {
+        // the pass and its hand-over, a chain on s_ with no side stream; the
+        // hand-over reads its epoch from device memory (gmt_push_sync_dev),
+        // so the recorded launch is right for every later pass.  One rank
+        // that is its own neighbour everywhere has no hand-over: the pass alone.
+        // (the host hooks of push_block are step_block's on the replay path)
+        push_pass(p - 2, ks_);
+        if (push_mask_) push_handover();
+      } else {
         enqueue_block(p - 2, ks_);
+      }
       e = gmt_rt_stream_end_capture(s_, p < 2 ? &graph_[p] : &graph2_[p - 2]);
     }
     fresh_[0] = saved[0];

@@ -375,6 +375,24 @@ int gmt_push_sync(const uint64_t* local, uint64_t* const remote[8], int mask, ui
   return 0;
 }
 
+// CPU backend of gmt_push_sync_dev: the hand-over of epoch *epoch + 1, then
+// *epoch advances.  One thread per call: it is the first and the last
+// arrival, so *arrivals goes 0 -> 1 -> 0 within the call.
+int gmt_push_sync_dev(const uint64_t* local, uint64_t* const remote[8], int mask, uint64_t* epoch,
+                      unsigned* arrivals, unsigned* err, unsigned* stop, void* stream) {
+  if (!local || !err || !epoch || !arrivals || mask < 0 || mask > 255) return 1;
+  for (int d = 0; d < 8; ++d)
+    if (((mask >> d) & 1) && (!remote || !remote[d])) return 1;
+  if (mask == 0) return 0;
+  if (stop && __atomic_load_n(stop, __ATOMIC_RELAXED) != 0) return 0;  // stopped: neither word is touched
+  const uint64_t e = __atomic_load_n(epoch, __ATOMIC_RELAXED) + 1;
+  __atomic_fetch_add(arrivals, 1u, __ATOMIC_ACQ_REL);
+  const int rc = gmt_push_sync(local, remote, mask, e, err, stop, stream);
+  __atomic_store_n(arrivals, 0u, __ATOMIC_RELAXED);
+  if (rc == 0) __atomic_store_n(epoch, e, __ATOMIC_RELEASE);
+  return rc;
+}
+
 int64_t gmt_jacobi5tb_group_cols(int sweeps, int wg_waves) {
   if (!gmt_jacobi5tb_supported(sweeps)) return 0;
   // the GPU kernel's strip geometry (gmt/tb_geom.h)

@@ -60,6 +60,10 @@ int gmt_engine_jacobi_exchange(void* h); /* one blocking halo exchange */
  * overlap_auto ns per pass with overlap, without (0 if not tuned), exact arithmetic in use,
  * band-first passes, inline halo exchange in use */
 int gmt_engine_jacobi_info(void* h, int64_t* out);
+/* Which passes replay from hipGraphs: bit 0 = the single sweeps, bit 1 = the
+ * full fused passes (tsteps sweeps; inline-halo passes with their hand-over).
+ * 0 without `graph`, on the CPU backend, or after a failed capture. */
+int gmt_engine_jacobi_graphs(void* h);
 /* The fused passes (sweeps per pass, in launch order) that run(steps) enqueues:
  * writes min(n, max) entries, returns n. */
 int gmt_engine_jacobi_plan(void* h, int steps, int* out, int max);

@@ -16,9 +16,14 @@
 //     passes run band-first: the boundary bands of the pass finish first
 //     and signal, and the exchange of the pass's OUTPUT runs under the rest
 //     of it (enqueue_block);
-//   * graph: with a stream-ordered transport (rccl, local) both step parities
-//     are captured into hipGraphs and replayed — one host call per step, so
-//     small per-GPU domains (strong scaling at 8 GPUs) are not launch-bound.
+//   * graph: with a stream-ordered transport (rccl, ipc, local) both step
+//     parities are captured into hipGraphs and replayed — one host call per
+//     step, so small per-GPU domains (strong scaling at 8 GPUs) are not
+//     launch-bound.  Fused passes are captured too, per parity: the serial
+//     pass with its exchange, the band-first pass with its forked exchange,
+//     and the inline-halo pass (push) with its hand-over, whose epoch lives
+//     in device memory (gmt_push_sync_dev) so a replay hands over the right
+//     one.  Partial passes (fewer sweeps than tsteps) stay eager.
 //
 //   * tblock: K = tsteps sweeps per kernel and per exchange (temporal
 //     blocking): u(t) is read once and u(t+K) written once (gmt_jacobi5tb,
@@ -79,7 +84,8 @@ struct JacobiConfig {
   // stores its output faces straight into the neighbours' ghost cells of
   // their next input (IPC mappings traded over the transport's control
   // plane; this rank's own buffers on a periodic axis), then one small
-  // hand-over launch (gmt_push_sync) replaces the halo exchange.  Needs a
+  // hand-over launch (gmt_push_sync_dev) replaces the halo exchange.  With
+  // `graph`, pass and hand-over replay from one hipGraph per parity.  Needs a
   // transport with a control plane (ipc) unless every neighbour is this
   // rank; off (the transport's exchange as before) when the share is too
   // small for the kernel's push rules.
@@ -144,6 +150,9 @@ class JacobiSolver {
   size_t bytes_per_exchange() const { return halo_[0] ? halo_[0]->bytes_sent() : 0; }
   size_t messages() const { return halo_[0] ? halo_[0]->messages() : 0; }
   bool graph_active() const { return graph_[0] != nullptr || graph2_[0] != nullptr; }
+  bool sweep_graph_active() const { return graph_[0] != nullptr; }  // the single sweeps replay
+  // the full fused passes (inline-halo ones with their hand-over) replay from hipGraphs
+  bool fused_graph_active() const { return graph2_[0] != nullptr; }
   bool tblock() const { return ks_ > 1; }
   int tsteps() const { return ks_; }
   int ghost() const { return g_; }
@@ -185,6 +194,8 @@ class JacobiSolver {
   void setup_push();
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
+  void push_pass(int parity, int k);   // the pass launch alone
+  void push_handover();                // the hand-over launch alone (push_mask_ != 0)
 
   comm::Transport& t_;
   JacobiConfig cfg_;
@@ -227,15 +238,16 @@ class JacobiSolver {
   // inline halo exchange (setup_push): per parity of the pass's INPUT, the
   // push targets (gmt_tb_opts.push) — the neighbours' other buffer with the
   // face translation folded in; the neighbours' flag slots for this rank;
-  // the directions that are other ranks; the hand-over epoch
+  // the directions that are other ranks; the hand-over epoch and the
+  // hand-over launch's arrival counter (device words: gmt_push_sync_dev)
   bool push_on_ = false;
   const double* push_base_[2][8] = {};
   uint64_t* push_remote_[8] = {};
   int push_mask_ = 0;
-  uint64_t push_epoch_ = 0;
   Buffer<uint64_t> push_flags_;  // [d]: written by the neighbour in direction d
   Buffer<unsigned> push_err_;    // host-visible: bit d = the wait for direction d expired
   Buffer<unsigned> push_stop_;   // device word: a wait expired, later passes return at once
+  Buffer<uint64_t> push_ctl_;    // device words: [0] hand-overs done (the epoch), [1] arrival counter
   Buffer<uint64_t> clk_;         // gmt_tb_opts.clock: cycles, 100 MHz ticks, samples
   std::vector<void*> push_opened_;
 };

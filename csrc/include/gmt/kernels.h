@@ -219,11 +219,14 @@ typedef struct gmt_tb_opts {
      segment planner keeps every segment clear of one of the S / N faces;
      no completion signal options; rects of even width or wider than a
      strip (no odd-edge stores).  A push pass runs the per-strip kernel
-     unless shared hand-off groups are asked for explicitly (`shared`). */
+     unless shared hand-off groups are asked for explicitly (`shared`).
+     Every argument of a push pass is fixed per buffer parity, and so are
+     those of the hand-over that follows it (gmt_push_sync_dev keeps its
+     epoch in memory): pass + hand-over can be captured into a hipGraph. */
   const double* push[8];
   int push_w;
   /* Inline-halo passes only (push_w > 0): a device word (NULL = none) that a
-     timed-out hand-over sets (gmt_push_sync `stop`); while it is non-zero
+     timed-out hand-over sets (gmt_push_sync / gmt_push_sync_dev `stop`); while it is non-zero
      every workgroup of the pass returns at entry — its ghost cells are
      stale and a late neighbour may still be writing them — and the job
      fails at its next synchronisation. */
@@ -304,9 +307,25 @@ int gmt_signal_wait(const uint64_t* signal, uint64_t* seen, unsigned* err, void*
  * the following passes, which then return at once) and gives up.  While
  * *stop is non-zero the hand-over neither signals nor waits, so a stalled
  * neighbour stops the whole job within one wait instead of one per pass.
- * local / remote: GMT_SPACE_FLAGS memory. */
+ * local / remote: GMT_SPACE_FLAGS memory.  The epoch is a launch argument:
+ * the caller counts the hand-overs, and a captured launch would replay a
+ * stale one (gmt_push_sync_dev is the form for hipGraphs). */
 int gmt_push_sync(const uint64_t* local, uint64_t* const remote[8], int mask, uint64_t epoch, unsigned* err,
                   unsigned* stop, void* stream);
+
+/* gmt_push_sync with the epoch in memory: the hand-over of epoch e = *epoch
+ * + 1, read at entry by each of the launch's 8 workgroups; the last one to
+ * finish (counted in *arrivals) stores e into *epoch and zeroes *arrivals.
+ * The launch's arguments are then the same for every pass, so one captured
+ * launch replays as the hand-over of every later pass, and eager and
+ * replayed hand-overs mix freely (the engine uses this form for both).
+ * epoch / arrivals: this rank's own words in device or GMT_SPACE_FLAGS
+ * memory, zeroed before the first hand-over, touched by nothing else;
+ * successive launches are ordered by the stream.  A launch that finds *stop
+ * non-zero touches neither word.  mask == 0 launches nothing and leaves
+ * *epoch alone.  err / stop / the wait bound: as gmt_push_sync. */
+int gmt_push_sync_dev(const uint64_t* local, uint64_t* const remote[8], int mask, uint64_t* epoch,
+                      unsigned* arrivals, unsigned* err, unsigned* stop, void* stream);
 
 /* Test hook: the XCD (XCC_ID) each of n one-wave workgroups of a single
  * launch ran on, out[i] for workgroup i (device memory).  gmt_push_sync's

@@ -229,6 +229,57 @@ __global__ __launch_bounds__(kWave) void push_sync_kernel(PushSyncArgs a) {
   __atomic_thread_fence(__ATOMIC_ACQUIRE);  // system scope, on this workgroup's XCD
 }
 
+// gmt_push_sync_dev: the same hand-over with its epoch in device memory, so
+// the launch's arguments are the same bytes for every pass and a captured
+// launch replays correctly (as gmt_ipc_plan.epoch above).  Every workgroup
+// reads *epoch at entry (e = *epoch + 1); the last of the 8 to arrive stores
+// e and resets the arrival counter, so no workgroup of this launch can still
+// be about to read the old value, and the next launch (ordered by the kernel
+// boundary) reads the new one.  No workgroup waits for another one of its
+// launch: the order the 8 are dispatched in does not matter.  A launch that
+// finds *stop set returns at entry on every workgroup and leaves both words
+// alone.  (A workgroup dispatched after another one of its launch has set
+// *stop leaves the counter short of 8: every later launch returns at entry
+// too, and the host aborts at its next synchronisation.)
+struct PushSyncDevArgs {
+  const uint64_t* local;
+  uint64_t* remote[8];
+  uint64_t* epoch;
+  unsigned* arrivals;
+  unsigned* err;
+  unsigned* stop;
+  uint64_t ticks;
+  int mask;
+};
+
+__global__ __launch_bounds__(kWave) void push_sync_dev_kernel(PushSyncDevArgs a) {
+  const int d = threadIdx.x;
+  if (a.stop && __hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+  const uint64_t e = __hip_atomic_load(a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+  const bool mine = d < 8 && ((a.mask >> d) & 1);
+  if (blockIdx.x == 0 && mine) {
+    // the pass's face stores are complete (stream order, as in push_sync_kernel)
+    __atomic_thread_fence(__ATOMIC_RELEASE);  // system scope
+    __hip_atomic_store(a.remote[d], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (mine) {
+    const uint64_t t0 = wall_clock64();
+    while (__hip_atomic_load(const_cast<uint64_t*>(a.local + d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < e) {
+      __builtin_amdgcn_s_sleep(2);
+      if (wall_clock64() - t0 > a.ticks) {
+        __hip_atomic_fetch_or(a.err, 1u << d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (a.stop) __hip_atomic_fetch_or(a.stop, 1u << d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);  // system scope, on this workgroup's XCD
+  // every lane of this workgroup read *epoch before the barrier above
+  if (d == 0 && last_arrival(a.arrivals, kNumXcd))
+    __hip_atomic_store(a.epoch, e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // per-wait bound in device wall-clock ticks (GMT_WAIT_TIMEOUT_MS, default 10 s)
 uint64_t timeout_ticks() {
   static int dev_cached = -1;
@@ -336,6 +387,27 @@ extern "C" int gmt_push_sync(const uint64_t* local, uint64_t* const remote[8], i
   a.mask = mask;
   if (mask == 0) return 0;
   ipc::push_sync_kernel<<<kNumXcd, kWave, 0, static_cast<hipStream_t>(stream)>>>(a);
+  GMT_RET_LAUNCH();
+}
+
+extern "C" int gmt_push_sync_dev(const uint64_t* local, uint64_t* const remote[8], int mask, uint64_t* epoch,
+                                 unsigned* arrivals, unsigned* err, unsigned* stop, void* stream) {
+  using namespace gmt;
+  if (!local || !err || !epoch || !arrivals || mask < 0 || mask > 255) return static_cast<int>(hipErrorInvalidValue);
+  ipc::PushSyncDevArgs a{};
+  a.local = local;
+  for (int d = 0; d < 8; ++d) {
+    a.remote[d] = remote ? remote[d] : nullptr;
+    if (((mask >> d) & 1) && !a.remote[d]) return static_cast<int>(hipErrorInvalidValue);
+  }
+  a.epoch = epoch;
+  a.arrivals = arrivals;
+  a.err = err;
+  a.stop = stop;
+  a.ticks = ipc::timeout_ticks();
+  a.mask = mask;
+  if (mask == 0) return 0;
+  ipc::push_sync_dev_kernel<<<kNumXcd, kWave, 0, static_cast<hipStream_t>(stream)>>>(a);
   GMT_RET_LAUNCH();
 }
 

@@ -110,6 +110,7 @@ _SIGS = {
     "gmt_jacobi5tb_push_shared_supported": (c_int, [c_int, c_int]),
     "gmt_jacobi5tb_shared_path": (c_int, [c_vp, c_int, c_vp, c_int]),
     "gmt_signal_wait": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gmt_push_sync_dev": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gmt_stage_copy": (c_int, [c_int, c_vp, c_vp, c_vp, ctypes.c_uint64, c_int, c_vp]),
     "gmt_stage_scatter": (c_int, [c_int, c_vp, c_int, c_vp]),
     "gmt_poly_check": (c_int, [c_i64, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp]),

@@ -96,6 +96,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_residual.restype = ctypes.c_double
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
     lib.gmt_engine_jacobi_info.restype = c_int
+    lib.gmt_engine_jacobi_graphs.argtypes = [vp]
+    lib.gmt_engine_jacobi_graphs.restype = c_int
     lib.gmt_engine_jacobi_tb_info.argtypes = [vp, c_int, ctypes.POINTER(i64)]
     lib.gmt_engine_jacobi_tb_info.restype = c_int
     lib.gmt_engine_jacobi_tb_shared.argtypes = [vp, c_int]
@@ -295,6 +297,9 @@ class NativeJacobi:
         mappings, then one hand-over launch; gmt/jacobi.hpp JacobiConfig::push).
         Needs the IPC transport when a neighbour is another rank; silently the
         transport's exchange when the share is too small (``push_active``).
+        With ``graph`` a full pass and its hand-over replay from one hipGraph
+        per parity (``graph_fused``; the hand-over's epoch lives in device
+        memory, gmt_push_sync_dev); partial passes stay eager.
         shared: gmt_tb_opts.shared of every fused pass, push passes included
         (JacobiConfig::tb_shared): -1 no shared hand-off groups, 0 the kernel's
         default (a push pass then runs the per-strip kernel), 1 / 4 groups of
@@ -360,6 +365,9 @@ class NativeJacobi:
         self.tsteps = int(tb)
         self.tblock = self.tsteps > 1
         self.graph = bool(graph_on)
+        # the full fused passes replay from hipGraphs (`graph` is true as soon
+        # as the single sweeps do); inline-halo passes replay with their hand-over
+        self.graph_fused = bool(self.lib.gmt_engine_jacobi_graphs(self.h) & 2)
         self.overlap = bool(overlap_on)
         self.transport = transport_label(kind, e)
 
