@@ -9,6 +9,8 @@
 //   copy2d     16 B/elem      (halo pack of a dim-0 face: strided 16-B reads)
 // CLI: gmt_kernel_bench [--daxpy-n=N] [--jacobi-n=N] [--iters=K] [--json=FILE]
 //      [--only=daxpy,jacobi,stencil,pack]
+//      --only=edges [--reps=5]: the boundary-band split of the derivative
+//      (gmt_stencil5_2d_edges / _interior) against the whole-field kernels
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -245,6 +247,49 @@ int main(int argc, char** argv) {
       GMT_CHECK("d1", gmt_stencil5_2d(1, b, a, c, 128.0, in.data(), b, out.data(), b, s));
     });
     report("stencil5", 1, "dim1 524288 x 1028->1024", ms, bytes);
+  }
+  if (only.find("edges") != std::string::npos) {
+    // --only=edges: the boundary-band split of the derivative at the
+    // reference's shapes, --reps=5 rounds that alternate the variants (clock
+    // drift hits all alike): the two 2-deep bands by one gmt_stencil5_2d_edges
+    // launch against two gmt_stencil5_2d launches on the band sub-rectangles
+    // (the only way without the band kernels), and interior + edges back to
+    // back against the single full launch.
+    const int64_t a = 1024, b = 512 * 1024;
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    Buffer<double> in(static_cast<size_t>(a + 4) * b, GMT_SPACE_DEVICE), out(static_cast<size_t>(a) * b, GMT_SPACE_DEVICE);
+    GMT_CHECK("fill", gmt_fill_poly(0, a + 4, b, 0.0, 1e-3, 0.0, 1e-3, in.data(), a + 4, s));
+    const double c[5] = {1.0 / 12, -2.0 / 3, 0.0, 2.0 / 3, -1.0 / 12};
+    for (int dim = 0; dim < 2; ++dim) {
+      const int64_t nx = dim == 0 ? a : b, ny = dim == 0 ? b : a, ld_in = dim == 0 ? a + 4 : b, ld_out = nx;
+      const int64_t hi_in = dim == 0 ? a - 2 : (a - 2) * ld_in, hi_out = dim == 0 ? a - 2 : (a - 2) * ld_out;
+      const int64_t bx = dim == 0 ? 2 : nx, by = dim == 0 ? ny : 2;
+      const std::function<void()> variant[4] = {
+          [&] {
+            GMT_CHECK("band lo", gmt_stencil5_2d(dim, bx, by, c, 128.0, in.data(), ld_in, out.data(), ld_out, s));
+            GMT_CHECK("band hi", gmt_stencil5_2d(dim, bx, by, c, 128.0, in.data() + hi_in, ld_in,
+                                                 out.data() + hi_out, ld_out, s));
+          },
+          [&] { GMT_CHECK("edges", gmt_stencil5_2d_edges(dim, nx, ny, c, 128.0, in.data(), ld_in, out.data(), ld_out, 3, s)); },
+          [&] { GMT_CHECK("full", gmt_stencil5_2d(dim, nx, ny, c, 128.0, in.data(), ld_in, out.data(), ld_out, s)); },
+          [&] {
+            GMT_CHECK("interior", gmt_stencil5_2d_interior(dim, nx, ny, c, 128.0, in.data(), ld_in, out.data(), ld_out, 3, s));
+            GMT_CHECK("edges", gmt_stencil5_2d_edges(dim, nx, ny, c, 128.0, in.data(), ld_in, out.data(), ld_out, 3, s));
+          }};
+      const char* name[4] = {"2 x stencil5_2d bands", "stencil5_2d_edges", "stencil5_2d full", "interior + edges"};
+      Stats st[4];
+      for (int rep = 0; rep < reps; ++rep)
+        for (int v = 0; v < 4; ++v) {
+          const double ms = time_ms(s, iters, variant[v]);
+          st[v].add(ms);
+          std::printf("edges dim%d rep %d  %-22s %9.4f ms\n", dim, rep, name[v], ms);
+        }
+      for (int v = 0; v < 4; ++v)
+        std::printf("edges dim%d summary %-22s min %9.4f  median %9.4f  max %9.4f ms  (range %.4f)\n", dim, name[v],
+                    st[v].min(), st[v].median(), st[v].max(), st[v].max() - st[v].min());
+      std::printf("edges dim%d  edges / bands = %.4f   (interior + edges) / full = %.4f  (medians)\n", dim,
+                  st[1].median() / st[0].median(), st[3].median() / st[2].median());
+    }
   }
   if (only.find("pack") != std::string::npos) {
     // dim-0 halo faces of the reference's field: 2 rows x 524288 columns, pitch 1028

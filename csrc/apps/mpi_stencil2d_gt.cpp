@@ -29,6 +29,17 @@
 //   --timeout=S           hang watchdog (gmt/watchdog.hpp)
 //   --check               compare the ghost rows with the analytic field after EVERY
 //                         exchange (GMT_CORRUPT_GHOST=R:K injects a bad cell); exit 5 on a mismatch
+//   --overlap             after each derivative test, time whole steps (exchange + derivative
+//                         through to completion) in two orders, interleaved: the serial one
+//                         above, and one that runs the exchange on a high-priority stream
+//                         beside the interior of the derivative and then the ghost-dependent
+//                         bands (gmt_stencil5_2d_interior / _edges, gmt/deriv.hpp).  One more
+//                         line per test, seconds summed over timed steps and ranks:
+//                         "STEP dim:%d, %s, buf:%d; serial=%0.8f, overlap=%0.8f [transport]";
+//                         err= is then the last overlapped step's.  With --check the line
+//                         carries step_err=, the largest err_norm any overlapped step's
+//                         derivative had on any rank; exit 5 above n_global / 192 (half of
+//                         what one stale ghost cell costs)
 //   --debug               the reference's DEBUG-build per-rank lines: "%d/%d exchange time
 //                         %0.8f ms" and "%d/%d [%d:0x%08x] err_norm = %.8f" after each
 //                         test_deriv, "%d/%d allreduce time %0.8f ms" after each test_sum
@@ -61,6 +72,7 @@ int main(int argc, char** argv) {
   const std::string tests = cli.get("tests", "deriv,sum");
   const std::string json = cli.get("json", "");
   const bool debug = cli.flag("debug");
+  const bool overlap = cli.flag("overlap");
 
   mpi_init_pinned(&argc, &argv);  // pinned near the GPU first (gmt/device.hpp)
   int world_size = 1, world_rank = 0;
@@ -111,10 +123,28 @@ int main(int argc, char** argv) {
     MPI_Reduce(&r.err_norm, &err_sum, 1, MPI_DOUBLE, MPI_SUM, 0, MPI_COMM_WORLD);
     double med = r.iters.median(), mx = 0;
     MPI_Allreduce(&med, &mx, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+    // --overlap: whole steps of both orders, aggregated like the exchange time
+    double step_sum[2] = {0, 0}, step_med[2] = {0, 0}, step_err = -1;
+    if (overlap) {
+      const double mine[2] = {r.step_serial.sum(), r.step_overlap.sum()};
+      const double med2[2] = {r.step_serial.median(), r.step_overlap.median()};
+      MPI_Reduce(mine, step_sum, 2, MPI_DOUBLE, MPI_SUM, 0, MPI_COMM_WORLD);
+      MPI_Reduce(med2, step_med, 2, MPI_DOUBLE, MPI_MAX, 0, MPI_COMM_WORLD);
+      MPI_Allreduce(&r.step_err_max, &step_err, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      // one stale ghost cell moves an edge value by scale / 12 = n_global / 96
+      if (step_err > static_cast<double>(n_global_deriv) / 192) halo_check_failed() = true;
+    }
     if (world_rank == 0) {
       std::printf("TEST dim:%d, %s, buf:%d; %0.8f, err=%0.8f%s\n", dim,
                   space == GMT_SPACE_MANAGED ? "managed" : "device ", buf ? 1 : 0, time_sum,
                   err_sum, tags(space, true).c_str());
+      if (overlap) {
+        char err_field[48] = "";
+        if (step_err >= 0) std::snprintf(err_field, sizeof(err_field), ", step_err=%0.8f", step_err);
+        std::printf("STEP dim:%d, %s, buf:%d; serial=%0.8f, overlap=%0.8f%s [%s]\n", dim,
+                    space == GMT_SPACE_MANAGED ? "managed" : "device ", buf ? 1 : 0, step_sum[0], step_sum[1],
+                    err_field, r.transport.c_str());
+      }
       JsonRecord j;
       j.add("app", "mpi_stencil2d_gt").add("test", name).add("dim", dim)
           .add("mem", space == GMT_SPACE_MANAGED ? "managed" : "device").add("buf", buf)
@@ -125,6 +155,11 @@ int main(int argc, char** argv) {
           .add("GBps_per_rank", mx > 0 ? r.bytes_per_exchange / mx / 1e9 : 0.0)
           .add("buffers", alloc_per_call ? "per-call" : "persistent")
           .add("managed_host_resident", space == GMT_SPACE_MANAGED && host_resident_managed);
+      if (overlap) {
+        j.add("step_serial_us_median_max_rank", step_med[0] * 1e6)
+            .add("step_overlap_us_median_max_rank", step_med[1] * 1e6)
+            .add("step_err_max", step_err);
+      }
       j.append_to(json);
     }
     std::fflush(stdout);
@@ -149,6 +184,7 @@ int main(int argc, char** argv) {
           c.host_init = cli.flag("host-init");
           c.host_verify = cli.flag("host-verify");
           c.check = cli.flag("check");
+          c.overlap = overlap;
           c.realloc_per_call = alloc_per_call;
           DerivResult r = run_deriv(c, b, MPI_COMM_WORLD, pool);
           report("deriv", dim, c.space, buf, r);

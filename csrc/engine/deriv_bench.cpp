@@ -49,3 +49,34 @@ extern "C" int gmt_engine_deriv_bench(int64_t n_local, int64_t n_other, int n_it
   out[13] = s.max_abs_err;
   return 0;
 }
+
+// The same two derivative tests with DerivConfig::overlap: whole steps
+// (exchange + derivative through to completion) in the serial and the
+// overlapped order, interleaved (gmt/deriv.hpp).
+extern "C" int gmt_engine_deriv_step_bench(int64_t n_local, int64_t n_other, int n_iter, int n_warmup,
+                                           int rank, int world, int transport, const void* ccl_id,
+                                           double* out, int check) {
+  std::unique_ptr<gmt::comm::Transport> t = gmt::engine_transport(rank, world, transport, ccl_id);
+  if (!t) return 1;
+  for (int dim = 0; dim < 2; ++dim) {
+    gmt::watchdog_kick(dim == 0 ? "engine: overlapped derivative steps dim 0" : "engine: overlapped derivative steps dim 1");
+    gmt::apps::DerivConfig c;
+    c.dim = dim;
+    c.n_local = static_cast<size_t>(n_local);
+    c.n_other = static_cast<size_t>(n_other);
+    c.n_iter = n_iter;
+    c.n_warmup = n_warmup;
+    c.buf = false;
+    c.check = check != 0;
+    c.overlap = true;
+    const gmt::apps::DerivResult r = gmt::apps::run_deriv_on(c, *t, rank, world);
+    double* o = out + 6 * dim;
+    o[0] = r.step_serial.median();
+    o[1] = r.step_overlap.median();
+    o[2] = r.err_norm;
+    o[3] = r.step_err_max;
+    o[4] = static_cast<double>(r.bad_ghosts);
+    o[5] = r.exact_norm;
+  }
+  return 0;
+}

@@ -54,6 +54,37 @@ int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const double* c, do
   return 0;
 }
 
+// the band rule of gmt/kernels.h: each band, then the rest, as a sub-rectangle
+int gmt_stencil5_2d_edges(int dim, int64_t nx_out, int64_t ny_out, const double* c, double scale,
+                          const double* in, int64_t ld_in, double* out, int64_t ld_out, int sides, void*) {
+  if ((dim != 0 && dim != 1) || (sides & ~3)) return 1;
+  if (nx_out <= 0 || ny_out <= 0) return 0;
+  const int64_t n = dim == 0 ? nx_out : ny_out;
+  int64_t lo_w, hi_w;
+  gmt_stencil5_bands(n, sides, &lo_w, &hi_w);
+  const int64_t start[2] = {0, n - hi_w}, w[2] = {lo_w, hi_w};
+  for (int k = 0; k < 2; ++k) {
+    if (w[k] <= 0) continue;
+    const int64_t oi = dim == 0 ? start[k] : start[k] * ld_in, oo = dim == 0 ? start[k] : start[k] * ld_out;
+    gmt_stencil5_2d(dim, dim == 0 ? w[k] : nx_out, dim == 0 ? ny_out : w[k], c, scale, in + oi, ld_in, out + oo,
+                    ld_out, nullptr);
+  }
+  return 0;
+}
+
+int gmt_stencil5_2d_interior(int dim, int64_t nx_out, int64_t ny_out, const double* c, double scale,
+                             const double* in, int64_t ld_in, double* out, int64_t ld_out, int sides, void*) {
+  if ((dim != 0 && dim != 1) || (sides & ~3)) return 1;
+  if (nx_out <= 0 || ny_out <= 0) return 0;
+  int64_t lo_w, hi_w;
+  gmt_stencil5_bands(dim == 0 ? nx_out : ny_out, sides, &lo_w, &hi_w);
+  if (dim == 0)
+    return gmt_stencil5_2d(0, nx_out - lo_w - hi_w, ny_out, c, scale, in + lo_w, ld_in, out + lo_w, ld_out,
+                           nullptr);
+  return gmt_stencil5_2d(1, nx_out, ny_out - lo_w - hi_w, c, scale, in + lo_w * ld_in, ld_in,
+                         out + lo_w * ld_out, ld_out, nullptr);
+}
+
 // one loop per entry point: no kernel to pick
 int gmt_stencil5_2d_path(int, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t* seg_rows) {
   if (seg_rows) *seg_rows = 0;

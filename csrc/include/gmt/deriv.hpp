@@ -57,6 +57,10 @@ struct DerivConfig {
   // chunk) differs by >= 1 and is counted.  The reference checks only the
   // last iteration's derivative (mpi_stencil2d_gt.cc:541-570).
   bool check = false;
+  // --overlap (opt-in): time whole steps — exchange + derivative through to
+  // completion — in two orders, the reference's serial one and one that
+  // hides the exchange under the interior of the derivative (run_deriv_on)
+  bool overlap = false;
 };
 
 struct DerivResult {
@@ -71,10 +75,18 @@ struct DerivResult {
   size_t bytes_per_exchange = 0;
   long long bad_ghosts = -1;  // --check: ghost cells that were wrong after some exchange (-1: not checked)
   int checked_exchanges = 0;
+  // overlap: whole-step seconds of the timed steps of each order, and with
+  // --check the largest err_norm any overlapped step's derivative had (-1:
+  // not checked)
+  Stats step_serial, step_overlap;
+  double step_err_max = -1;
 };
 
 // GMT_CORRUPT_GHOST=R:K (fault injection for --check): rank R overwrites one
-// ghost cell after its K-th exchange (counting warm-ups from 0)
+// ghost cell after its K-th exchange (counting warm-ups from 0).  With
+// overlap: in the overlapped step of its K-th iteration, after finish() and
+// before the edges kernel, it puts one ghost cell back to its value of the
+// step before — what a late or stale ghost cell would hold.
 inline bool corrupt_ghost_now(int rank, int it) {
   const char* e = std::getenv("GMT_CORRUPT_GHOST");
   if (!e) return false;
@@ -190,7 +202,113 @@ inline DerivResult run_deriv_on(const DerivConfig& c, comm::Transport& tr, int r
         ghosts.push_back({&zf(0, n_bnd + c.n_local), static_cast<int64_t>(c.n_other), static_cast<int64_t>(n_bnd), 0.0, hi_c});
     }
   }
-  for (int it = 0; it < c.n_warmup + c.n_iter; ++it) {
+  if (c.overlap) {
+    // Whole steps in two orders.  Serial (the reference,
+    // mpi_stencil2d_gt.cc:511-535): blocking exchange, full derivative, sync.
+    // Overlapped: the exchange on a high-priority stream, the interior of
+    // the derivative beside it, then the ghost-dependent bands.  The
+    // interior (gmt/kernels.h band rule) reads no ghost cell, and the faces
+    // the exchange sends are only read by both, so the two streams share no
+    // hazard until the edges kernel, which waits for the unpacked ghosts.
+    // A side without a neighbour has fixed ghosts: it goes to the interior.
+    gmt_stream_t cs = nullptr;
+    gmt_event_t ev_packed = nullptr, ev_halo = nullptr;
+    GMT_CHECK("comm stream", gmt_rt_stream_create(&cs, 1));
+    GMT_CHECK("event", gmt_rt_event_create(&ev_packed, 0));
+    GMT_CHECK("event", gmt_rt_event_create(&ev_halo, 0));
+    const int sides = (lo >= 0 ? 1 : 0) | (hi >= 0 ? 2 : 0);
+    Buffer<double> exact, err_ws;
+    if (c.check) {  // the analytic derivative, once: every overlapped step is compared with it
+      exact = Buffer<double>(nx_out * ny_out, GMT_SPACE_DEVICE);
+      err_ws = Buffer<double>(gmt_diff_sq_workspace(nx_out, ny_out) + 1, GMT_SPACE_DEVICE);
+      GMT_CHECK("fill exact", gmt_fill_poly(d0 ? 1 : 2, nx_out, ny_out, x0, delta, y0, delta, exact.data(),
+                                            nx_out, s));
+      r.step_err_max = 0.0;
+    }
+    int raised = 0;
+    auto raise = [&] {  // outside the timed region
+      if (!c.check) return;
+      GMT_CHECK("raise", gmt_add_scalar(nrows, ncols, 1.0, z.data(), nrows, s));
+      GMT_CHECK("raise sync", gmt_rt_stream_synchronize(s));
+      ++raised;
+    };
+    auto check_ghosts = [&] {  // after the step's clock has stopped: the derivative left them alone
+      if (!c.check) return;
+      for (const Ghost& g : ghosts)
+        GMT_CHECK("ghost check", gmt_poly_check(g.nx, g.ny, g.x0, delta, g.y0, delta, static_cast<double>(raised),
+                                                1e-9, g.p, nrows, bad.data(), s));
+      ++r.checked_exchanges;
+    };
+    auto serial_step = [&](bool timed) {
+      raise();
+      const double t0 = wtime();
+      if (c.realloc_per_call) halo = std::make_unique<Halo2D>(tr, zf, gx, gy, nb, pack_y, buf_space);
+      halo->exchange(s);
+      const double t1 = wtime();
+      GMT_CHECK("stencil", gmt_stencil5_2d(c.dim, nx_out, ny_out, kDeriv5, scale, z.data(), nrows,
+                                           dz.data(), nx_out, s));
+      GMT_CHECK("stencil sync", gmt_rt_stream_synchronize(s));
+      const double t2 = wtime();
+      check_ghosts();
+      if (!timed) return;
+      r.total_time += t1 - t0;
+      r.iters.add(t1 - t0);
+      r.step_serial.add(t2 - t0);
+    };
+    auto overlap_step = [&](bool timed, bool corrupt) {
+      // the derivative does not see the raise: clear the last step's (equal) values,
+      // so that a cell this step leaves out is an error and not a survivor
+      if (c.check) GMT_CHECK("dz = 0", gmt_rt_memset_async(dz.data(), 0, dz.bytes(), s));
+      raise();
+      const double t0 = wtime();
+      if (c.realloc_per_call) halo = std::make_unique<Halo2D>(tr, zf, gx, gy, nb, pack_y, buf_space);
+      // the exchange first: the interior launch is held until the faces are
+      // packed, so the transfer is in flight before the interior takes the CUs
+      halo->start(cs, ev_packed);
+      if (halo->active()) GMT_CHECK("wait packed", gmt_rt_stream_wait_event(s, ev_packed));
+      GMT_CHECK("interior", gmt_stencil5_2d_interior(c.dim, nx_out, ny_out, kDeriv5, scale, z.data(), nrows,
+                                                     dz.data(), nx_out, sides, s));
+      halo->finish(cs);
+      if (corrupt && !ghosts.empty()) GMT_CHECK("corrupt", gmt_add_scalar(1, 1, -1.0, ghosts[0].p, nrows, cs));
+      GMT_CHECK("event", gmt_rt_event_record(ev_halo, cs));
+      GMT_CHECK("wait halo", gmt_rt_stream_wait_event(s, ev_halo));
+      GMT_CHECK("edges", gmt_stencil5_2d_edges(c.dim, nx_out, ny_out, kDeriv5, scale, z.data(), nrows,
+                                               dz.data(), nx_out, sides, s));
+      GMT_CHECK("comm sync", gmt_rt_stream_synchronize(cs));
+      GMT_CHECK("step sync", gmt_rt_stream_synchronize(s));
+      halo->check();
+      const double t1 = wtime();
+      check_ghosts();
+      if (c.check) {
+        double acc = 0.0;
+        GMT_CHECK("diff_sq", gmt_diff_sq(nx_out, ny_out, dz.data(), nx_out, exact.data(), nx_out, err_ws.data(),
+                                         err_ws.data() + 1, s));
+        GMT_CHECK("err D2H", gmt_rt_memcpy_async(&acc, err_ws.data(), sizeof(double), s));
+        GMT_CHECK("err sync", gmt_rt_stream_synchronize(s));
+        r.step_err_max = std::max(r.step_err_max, std::sqrt(acc));
+      }
+      if (timed) r.step_overlap.add(t1 - t0);
+    };
+    // one step of each order per iteration, serial / overlap / overlap /
+    // serial ... so neither order always runs second (clock and cache drift);
+    // the last step is an overlapped one: err_norm below is taken from it
+    const int n_it = c.n_warmup + c.n_iter;
+    for (int it = 0; it < n_it; ++it) {
+      const bool timed = it >= c.n_warmup, corrupt = c.check && corrupt_ghost_now(rank, it);
+      if ((n_it - 1 - it) % 2 == 0) {
+        serial_step(timed);
+        overlap_step(timed, corrupt);
+      } else {
+        overlap_step(timed, corrupt);
+        serial_step(timed);
+      }
+    }
+    gmt_rt_event_destroy(ev_packed);
+    gmt_rt_event_destroy(ev_halo);
+    gmt_rt_stream_destroy(cs);
+  }
+  // the reference's loop: exchanges timed alone (not run with overlap, which timed its own serial steps)
+  for (int it = 0; !c.overlap && it < c.n_warmup + c.n_iter; ++it) {
     if (c.check) GMT_CHECK("raise", gmt_add_scalar(nrows, ncols, 1.0, z.data(), nrows, s));
     if (c.check) GMT_CHECK("raise sync", gmt_rt_stream_synchronize(s));
     const double t0 = wtime();

@@ -124,6 +124,17 @@ void gmt_engine_watchdog_epitaph(const char* json, int code);
  * gmt/deriv.hpp; -1 without check). */
 int gmt_engine_deriv_bench(int64_t n_local, int64_t n_other, int n_iter, int n_warmup, int rank,
                            int world, int transport, const void* ccl_id, double* out, int check);
+/* The two derivative tests of gmt_engine_deriv_bench as whole steps
+ * (exchange + derivative through to completion) in two orders, interleaved
+ * (gmt/deriv.hpp DerivConfig::overlap): the serial one, and the exchange on
+ * a high-priority stream beside the interior of the derivative, then the
+ * ghost-dependent bands.  out[12]: per dim d (6 values at 6*d): serial step
+ * median seconds, overlapped step median seconds, err_norm of the last
+ * (overlapped) step, the largest err_norm of any overlapped step (check != 0;
+ * else -1), ghost cells found wrong (check != 0; else -1), norm of the
+ * analytic derivative. */
+int gmt_engine_deriv_step_bench(int64_t n_local, int64_t n_other, int n_iter, int n_warmup, int rank,
+                                int world, int transport, const void* ccl_id, double* out, int check);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,36 @@ enum { GMT_PATH_NONE = 0, GMT_PATH_SCALAR = 1, GMT_PATH_PT = 2, GMT_PATH_D1_WIN 
 int gmt_stencil5_2d_path(int dim, int64_t nx_out, int64_t ny_out, const double* in, int64_t ld_in,
                          const double* out, int64_t ld_out, int64_t* seg_rows);
 
+/* ---- The same stencil split for a step that overlaps the halo exchange with
+ *      the derivative: the cells that read ghost cells (the edges) and the
+ *      rest (the interior).
+ *
+ *      Band rule: n = the output extent along `dim`; `sides` bit 0 selects
+ *      the low end, bit 1 the high end;
+ *        lo_w = (sides & 1) ? min(2, n) : 0
+ *        hi_w = (sides & 2) ? min(2, n - lo_w) : 0
+ *      the edges are the indices [0, lo_w) and [n - hi_w, n) along `dim`, the
+ *      interior is [lo_w, n - hi_w): disjoint, and together the whole output
+ *      for every n >= 0 (2 = the ghost depth of a 5-tap stencil: an output
+ *      further in reads no ghost cell).
+ *
+ *      gmt_stencil5_2d_edges takes gmt_stencil5_2d's arguments (`in` / `out`
+ *      of the WHOLE output) and writes only the edge cells, both sides in one
+ *      launch of a kernel shaped for narrow bands; sides == 0 or an empty
+ *      band launches nothing.  gmt_stencil5_2d_interior runs gmt_stencil5_2d
+ *      on the interior sub-rectangle (an empty one launches nothing). */
+static inline void gmt_stencil5_bands(int64_t n, int sides, int64_t* lo_w, int64_t* hi_w) {
+  if (n < 0) n = 0;
+  *lo_w = (sides & 1) ? (n < 2 ? n : 2) : 0;
+  *hi_w = (sides & 2) ? (n - *lo_w < 2 ? n - *lo_w : 2) : 0;
+}
+int gmt_stencil5_2d_edges(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
+                          double scale, const double* in, int64_t ld_in, double* out,
+                          int64_t ld_out, int sides, void* stream);
+int gmt_stencil5_2d_interior(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
+                             double scale, const double* in, int64_t ld_in, double* out,
+                             int64_t ld_out, int sides, void* stream);
+
 /* ---- K6/K7/K8: batched strided 2-D copy (halo pack / unpack, fused L+R).
  *      Each descriptor copies `height` rows of `width` elements of
  *      `elem_bytes` (4 or 8) from src (row pitch src_ld elements) to dst

@@ -86,6 +86,91 @@ __global__ __launch_bounds__(kBlock) void stencil5_scalar(int dim, int64_t nx_ou
   out[y * ld_out + x] = acc;
 }
 
+// ---- Boundary bands (gmt_stencil5_2d_edges, the band rule of gmt/kernels.h):
+// the cells of an overlapped step that read ghost cells, both sides in one
+// launch.  The production kernels above are shaped for whole fields: a dim-0
+// band is 2 columns of every row, which stencil5_pt<0> would run with one
+// active lane per wave.
+struct Bands5 {
+  int64_t start[2];  // first output index along `dim` of each band
+  int w[2];          // its width: 0 (absent), 1 or 2
+  int n;             // bands in use: the present ones come first
+};
+
+// dim 0: lanes over rows.  A lane's band is 2 outputs from 6 contiguous
+// inputs (three 16-byte loads, one 16-byte store), and it does every band of
+// its row, so the loads of both ends are in flight together.  Needs the
+// vector conditions of plan5 and an even extent (bands 2 wide at even x).
+__global__ __launch_bounds__(kBlock) void stencil5_edges_d0(int64_t ny_out, Bands5 b, Coef5 cf, double scale,
+                                                            const double* __restrict__ in, int64_t ld_in,
+                                                            double* __restrict__ out, int64_t ld_out) {
+  const int64_t y = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (y >= ny_out) return;
+  const double c0 = cf.c[0] * scale, c1 = cf.c[1] * scale, c2 = cf.c[2] * scale,
+               c3 = cf.c[3] * scale, c4 = cf.c[4] * scale;
+  d2 a[2], m[2], e[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+    if (k < b.n) {
+      const double* p = in + y * ld_in + b.start[k];
+      a[k] = ld2(p), m[k] = ld2(p + 2), e[k] = ld2(p + 4);
+    }
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+    if (k < b.n) {
+      d2 o;
+      o.x = c0 * a[k].x + c1 * a[k].y + c2 * m[k].x + c3 * m[k].y + c4 * e[k].x;
+      o.y = c0 * a[k].y + c1 * m[k].x + c2 * m[k].y + c3 * e[k].x + c4 * e[k].y;
+      st2_nt(out + y * ld_out + b.start[k], o);
+    }
+}
+
+// dim 1: a band is one or two whole contiguous rows.  One column pair per
+// lane, 512 columns per block, blockIdx.y = the band: 5 or 6 coalesced
+// 16-byte loads for the band's 1 or 2 output pairs.
+__global__ __launch_bounds__(kBlock) void stencil5_edges_d1(int64_t nx_out, Bands5 b, Coef5 cf, double scale,
+                                                            const double* __restrict__ in, int64_t ld_in,
+                                                            double* __restrict__ out, int64_t ld_out) {
+  const int64_t x = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * 2;
+  if (x >= nx_out) return;
+  const int k = blockIdx.y;
+  const bool two = b.w[k] == 2;
+  const double c0 = cf.c[0] * scale, c1 = cf.c[1] * scale, c2 = cf.c[2] * scale,
+               c3 = cf.c[3] * scale, c4 = cf.c[4] * scale;
+  const double* p = in + b.start[k] * ld_in + x;
+  double* q = out + b.start[k] * ld_out + x;
+  if (x + 1 < nx_out) {
+    const d2 r0 = ld2(p), r1 = ld2(p + ld_in), r2 = ld2(p + 2 * ld_in), r3 = ld2(p + 3 * ld_in),
+             r4 = ld2(p + 4 * ld_in);
+    st2_nt(q, c0 * r0 + c1 * r1 + c2 * r2 + c3 * r3 + c4 * r4);
+    if (two) st2_nt(q + ld_out, c0 * r1 + c1 * r2 + c2 * r3 + c3 * r4 + c4 * ld2(p + 5 * ld_in));
+  } else {  // the last column of an odd width
+    const double r0 = p[0], r1 = p[ld_in], r2 = p[2 * ld_in], r3 = p[3 * ld_in], r4 = p[4 * ld_in];
+    q[0] = c0 * r0 + c1 * r1 + c2 * r2 + c3 * r3 + c4 * r4;
+    if (two) q[ld_out] = c0 * r1 + c1 * r2 + c2 * r3 + c3 * r4 + c4 * p[5 * ld_in];
+  }
+}
+
+// Unaligned views, odd pitches, odd dim-0 extents: one band cell per lane.
+// wtot = the bands' widths together, n_other = the extent across `dim`.
+__global__ __launch_bounds__(kBlock) void stencil5_edges_scalar(int dim, int64_t n_other, int wtot, Bands5 b,
+                                                                Coef5 cf, double scale, const double* in,
+                                                                int64_t ld_in, double* out, int64_t ld_out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n_other * wtot) return;
+  // dim 0: the band cells of a row are neighbours in i; dim 1: a band row's cells are
+  const int64_t o = dim == 0 ? i / wtot : i % n_other;
+  const int j = static_cast<int>(dim == 0 ? i % wtot : i / n_other);
+  const int64_t along = j < b.w[0] ? b.start[0] + j : b.start[1] + (j - b.w[0]);
+  const int64_t x = dim == 0 ? along : o, y = dim == 0 ? o : along;
+  const int64_t step = dim == 0 ? 1 : ld_in;
+  const double* p = in + y * ld_in + x;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) acc += cf.c[k] * scale * p[k * step];
+  out[y * ld_out + x] = acc;
+}
+
 static Coef5 make_coef(const double* c5) {
   Coef5 c;
   for (int k = 0; k < 5; ++k) c.c[k] = c5[k];
@@ -193,6 +278,51 @@ extern "C" int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const do
     }
   }
   GMT_RET_LAUNCH();
+}
+
+extern "C" int gmt_stencil5_2d_edges(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
+                                     double scale, const double* in, int64_t ld_in, double* out,
+                                     int64_t ld_out, int sides, void* stream) {
+  using namespace gmt;
+  if ((dim != 0 && dim != 1) || (sides & ~3)) return static_cast<int>(hipErrorInvalidValue);
+  if (nx_out <= 0 || ny_out <= 0) return 0;
+  const int64_t n = dim == 0 ? nx_out : ny_out, n_other = dim == 0 ? ny_out : nx_out;
+  int64_t lo_w, hi_w;
+  gmt_stencil5_bands(n, sides, &lo_w, &hi_w);
+  Bands5 b{};
+  if (lo_w > 0) b.start[b.n] = 0, b.w[b.n++] = static_cast<int>(lo_w);
+  if (hi_w > 0) b.start[b.n] = n - hi_w, b.w[b.n++] = static_cast<int>(hi_w);
+  if (b.n == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Coef5 cf = make_coef(coef5);
+  const bool vec_ok = aligned16(in) && aligned16(out) && (ld_in % 2 == 0) && (ld_out % 2 == 0);
+  if (vec_ok && dim == 0 && n % 2 == 0) {  // every band 2 wide, at an even x
+    stencil5_edges_d0<<<grid_1d((n_other + kBlock - 1) / kBlock), kBlock, 0, s>>>(n_other, b, cf, scale, in, ld_in,
+                                                                                  out, ld_out);
+  } else if (vec_ok && dim == 1) {
+    const dim3 grid(grid_1d((n_other + 2 * kBlock - 1) / (2 * kBlock)), b.n);
+    stencil5_edges_d1<<<grid, kBlock, 0, s>>>(n_other, b, cf, scale, in, ld_in, out, ld_out);
+  } else {
+    const int wtot = b.w[0] + b.w[1];
+    stencil5_edges_scalar<<<grid_1d((n_other * wtot + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+        dim, n_other, wtot, b, cf, scale, in, ld_in, out, ld_out);
+  }
+  GMT_RET_LAUNCH();
+}
+
+extern "C" int gmt_stencil5_2d_interior(int dim, int64_t nx_out, int64_t ny_out, const double* coef5,
+                                        double scale, const double* in, int64_t ld_in, double* out,
+                                        int64_t ld_out, int sides, void* stream) {
+  if ((dim != 0 && dim != 1) || (sides & ~3)) return static_cast<int>(hipErrorInvalidValue);
+  if (nx_out <= 0 || ny_out <= 0) return 0;
+  int64_t lo_w, hi_w;
+  gmt_stencil5_bands(dim == 0 ? nx_out : ny_out, sides, &lo_w, &hi_w);
+  // the sub-rectangle between the bands, by pointer arithmetic: the production kernels run it
+  if (dim == 0)
+    return gmt_stencil5_2d(0, nx_out - lo_w - hi_w, ny_out, coef5, scale, in + lo_w, ld_in, out + lo_w, ld_out,
+                           stream);
+  return gmt_stencil5_2d(1, nx_out, ny_out - lo_w - hi_w, coef5, scale, in + lo_w * ld_in, ld_in,
+                         out + lo_w * ld_out, ld_out, stream);
 }
 
 extern "C" int gmt_stencil5_1d(int64_t n_out, const double* coef5, double scale,

@@ -80,6 +80,8 @@ _SIGS = {
     "gmt_daxpy": (c_int, [c_i64, c_dbl, c_vp, c_vp, c_vp]),
     "gmt_stencil5_1d": (c_int, [c_i64, c_vp, c_dbl, c_vp, c_vp, c_vp]),
     "gmt_stencil5_2d": (c_int, [c_int, c_i64, c_i64, c_vp, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_stencil5_2d_edges": (c_int, [c_int, c_i64, c_i64, c_vp, c_dbl, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "gmt_stencil5_2d_interior": (c_int, [c_int, c_i64, c_i64, c_vp, c_dbl, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
     "gmt_stencil5_2d_path": (c_int, [c_int, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_jacobi5_path": (c_int, [c_i64, c_vp, c_vp, c_i64, c_vp, c_i64]),
     "gmt_copy2d_batched": (c_int, [c_int, c_vp, c_int, c_vp]),

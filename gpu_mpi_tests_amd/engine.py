@@ -117,6 +117,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_backend.restype = ctypes.c_char_p
     lib.gmt_engine_deriv_bench.argtypes = [i64, i64, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int]
     lib.gmt_engine_deriv_bench.restype = c_int
+    lib.gmt_engine_deriv_step_bench.argtypes = [i64, i64, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int]
+    lib.gmt_engine_deriv_step_bench.restype = c_int
     lib.gmt_engine_watchdog_kick.argtypes = [ctypes.c_char_p]
     lib.gmt_engine_watchdog_kick.restype = None
     lib.gmt_engine_watchdog_epitaph.argtypes = [ctypes.c_char_p, c_int]
@@ -509,6 +511,38 @@ def deriv_bench(n_local: int = 1024, n_other: int = 512 * 1024, n_iter: int = 10
                               err_norm=o[5], exact_norm=v[14 + d], bad_ghosts=int(v[16 + d]))
     res["allreduce_median_s"] = v[12]
     res["allreduce_max_rel_err"] = v[13]
+    res["transport"] = transport_label({LOCAL: "local", RCCL: "rccl", IPC: "ipc"}[transport], e)
+    return res
+
+
+def deriv_step_bench(n_local: int = 1024, n_other: int = 512 * 1024, n_iter: int = 100,
+                     n_warmup: int = 5, env: "gdist.DistEnv | None" = None, transport: str = "auto",
+                     check: bool = False) -> dict:
+    """The two derivative tests of :func:`deriv_bench` as whole steps (halo
+    exchange + derivative through to completion), timed in two interleaved
+    orders: serial (blocking exchange, then the full derivative) and
+    overlapped (the exchange on a high-priority stream beside the interior of
+    the derivative, then the ghost-dependent bands: ``gmt_stencil5_2d_interior``
+    / ``gmt_stencil5_2d_edges``).  Per dim: this rank's ``serial_median_s`` and
+    ``overlap_median_s``, the last (overlapped) step's ``err_norm``, and with
+    ``check`` the largest err_norm of any overlapped step (``step_err_max``)
+    and the ghost cells found wrong after any exchange (``bad_ghosts``); both
+    -1 without.  Collective: every rank calls it."""
+    e = env or gdist.get()
+    lib = load("cuda" if e.is_gpu else "cpu")
+    transport, cid = _transport_args(lib, e, transport)
+    out = (ctypes.c_double * 12)()
+    with _StdoutToStderr():
+        err = lib.gmt_engine_deriv_step_bench(int(n_local), int(n_other), int(n_iter), int(n_warmup), e.rank,
+                                              e.world_size, transport, cid, out, int(bool(check)))
+    if err:
+        raise EngineError(f"gmt_engine_deriv_step_bench failed: {err}")
+    v = list(out)
+    res = {}
+    for d in (0, 1):
+        o = v[6 * d:6 * d + 6]
+        res[f"dim{d}"] = dict(serial_median_s=o[0], overlap_median_s=o[1], err_norm=o[2], step_err_max=o[3],
+                              bad_ghosts=int(o[4]), exact_norm=o[5])
     res["transport"] = transport_label({LOCAL: "local", RCCL: "rccl", IPC: "ipc"}[transport], e)
     return res
 

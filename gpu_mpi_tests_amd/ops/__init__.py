@@ -1,7 +1,8 @@
 """Compute ops: hand-written gfx950 HIP kernels (libgmt) behind torch-facing wrappers.
 
 Kernel inventory: K1/K2 ``daxpy``; K3 ``stencil5_1d``;
-K4/K5/K11 ``stencil5_2d``; K6/K7/K8 ``copy2d_batched`` (halo pack/unpack);
+K4/K5/K11 ``stencil5_2d`` (and its ``stencil5_2d_edges`` /
+``stencil5_2d_interior`` split for overlapped steps); K6/K7/K8 ``copy2d_batched`` (halo pack/unpack);
 K9 ``sum_axis``; K10/K12 ``diff_sq``/``diff_norm``; analytic ``fill_poly``;
 and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep)
 and ``jacobi5tb`` (K fused sweeps per memory pass).
@@ -32,7 +33,10 @@ from .kernels import (  # noqa: F401
     tb_supported,
     stencil5_1d,
     stencil5_2d,
+    stencil5_2d_edges,
+    stencil5_2d_interior,
     stencil5_2d_path,
+    stencil5_bands,
     sum_axis,
     vsum,
 )

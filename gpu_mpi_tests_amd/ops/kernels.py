@@ -106,6 +106,59 @@ def stencil5_2d(inp: torch.Tensor, dim: int, out: torch.Tensor | None = None,
     return out
 
 
+def stencil5_bands(n: int, sides: int) -> tuple[int, int]:
+    """``(lo_w, hi_w)`` of the band rule (gmt/kernels.h): the edges of an output
+    of extent ``n`` along the stencil's axis are ``[0, lo_w)`` and
+    ``[n - hi_w, n)``, the interior is ``[lo_w, n - hi_w)``."""
+    n = max(int(n), 0)
+    lo_w = min(2, n) if sides & 1 else 0
+    hi_w = min(2, n - lo_w) if sides & 2 else 0
+    return lo_w, hi_w
+
+
+def _stencil5_2d_part(name: str, inp, dim, out, sides, scale, coef):
+    _check2d(inp, f"{name}.inp")
+    _check2d(out, f"{name}.out")
+    if dim not in (0, 1) or sides not in (0, 1, 2, 3):
+        raise ValueError(f"{name}: dim must be 0 or 1 and sides 0..3, got dim {dim}, sides {sides}")
+    ny_in, nx_in = inp.shape
+    nx_out, ny_out = (nx_in - 4, ny_in) if dim == 0 else (nx_in, ny_in - 4)
+    assert tuple(out.shape) == (ny_out, nx_out), (out.shape, ny_out, nx_out)
+    if not _is_dev(inp):
+        n = nx_out if dim == 0 else ny_out
+        lo_w, hi_w = stencil5_bands(n, sides)
+        spans = [(0, lo_w), (n - hi_w, n)] if name.endswith("edges") else [(lo_w, n - hi_w)]
+        r = ref.stencil5_2d(inp, dim, scale, coef)
+        for a, b in spans:
+            if dim == 0:
+                out[:, a:b] = r[:, a:b]
+            else:
+                out[a:b, :] = r[a:b, :]
+        return out
+    L = _native.lib()
+    cf = _Coef(coef)
+    fn = getattr(L, f"gmt_{name}")
+    _native.check(fn(dim, nx_out, ny_out, cf.ptr, float(scale), inp.data_ptr(), inp.stride(0),
+                     out.data_ptr(), out.stride(0), int(sides), _stream(inp)), f"gmt_{name}")
+    return out
+
+
+def stencil5_2d_edges(inp: torch.Tensor, dim: int, out: torch.Tensor, sides: int = 3,
+                      scale: float = 1.0, coef=DERIV5) -> torch.Tensor:
+    """The cells of :func:`stencil5_2d`'s output that read ghost cells: the
+    2-deep bands at the low (``sides`` bit 0) and high (bit 1) end along
+    ``dim``, both in one launch of the band kernel; no other cell of ``out``
+    is written (:func:`stencil5_bands`)."""
+    return _stencil5_2d_part("stencil5_2d_edges", inp, dim, out, sides, scale, coef)
+
+
+def stencil5_2d_interior(inp: torch.Tensor, dim: int, out: torch.Tensor, sides: int = 3,
+                         scale: float = 1.0, coef=DERIV5) -> torch.Tensor:
+    """The complement of :func:`stencil5_2d_edges` for the same ``sides``, by
+    the production kernels on the sub-rectangle between the bands."""
+    return _stencil5_2d_part("stencil5_2d_interior", inp, dim, out, sides, scale, coef)
+
+
 # gmt/kernels.h GMT_PATH_*: the kernel a launcher picks
 PATH_NONE, PATH_SCALAR, PATH_PT, PATH_D1_WIN, PATH_D1_DMA = range(5)
 
