@@ -11,6 +11,8 @@
 //      [--only=daxpy,jacobi,stencil,pack]
 //      --only=edges [--reps=5]: the boundary-band split of the derivative
 //      (gmt_stencil5_2d_edges / _interior) against the whole-field kernels
+//      --only=resid [--reps=5]: the read-only Jacobi residual (8 B/point) against
+//      the sweep with residual (16 B/point) and gmt_sum, at 8192^2 and 32768^2
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -289,6 +291,57 @@ int main(int argc, char** argv) {
                     st[v].min(), st[v].median(), st[v].max(), st[v].max() - st[v].min());
       std::printf("edges dim%d  edges / bands = %.4f   (interior + edges) / full = %.4f  (medians)\n", dim,
                   st[1].median() / st[0].median(), st[3].median() / st[2].median());
+    }
+  }
+  if (only.find("resid") != std::string::npos) {
+    // --only=resid: the read-only residual (gmt_jacobi5_resid, A) against
+    // what a residual cost before it existed (gmt_jacobi5 with resid: a whole
+    // sweep, B) and the read-only streaming yardstick (gmt_sum over the same
+    // number of doubles, C), at 8192^2 and 32768^2, --reps=5 rounds in the
+    // order A B C C B A (clock drift hits all alike); the best of the rounds
+    // is the figure compared.  --resid-n=N: one size only.
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    std::vector<int64_t> sizes = {8192, 32768};
+    if (cli.has("resid-n")) sizes = {static_cast<int64_t>(cli.geti("resid-n", 8192))};
+    for (const int64_t n : sizes) {
+      const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64;
+      Buffer<double> u(static_cast<size_t>(ld) * (n + 2), GMT_SPACE_DEVICE), un(u.size(), GMT_SPACE_DEVICE);
+      GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, u.data(), ld, s));
+      GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, un.data(), ld, s));
+      Buffer<double> ws(static_cast<size_t>(gmt_jacobi5_resid_workspace(n, n)), GMT_SPACE_DEVICE), out(2, GMT_SPACE_DEVICE);
+      Buffer<double> rws(static_cast<size_t>(gmt_jacobi_resid_workspace(n, n)) + 1, GMT_SPACE_DEVICE);
+      Buffer<double> sws(static_cast<size_t>(gmt_sum_workspace(n * n)) + 1, GMT_SPACE_DEVICE);
+      const std::function<void()> variant[3] = {
+          [&] {
+            GMT_CHECK("resid", gmt_jacobi5_resid(xo, n, 1, n, u.data(), ld, nullptr, 0, 0.25, 0.0, out.data(), ws.data(), s));
+          },
+          [&] {
+            GMT_CHECK("jacobi+resid", gmt_jacobi5(xo, n, 1, n, u.data(), un.data(), ld, nullptr, 0, 0.25, 0.0, rws.data(), s));
+          },
+          [&] { GMT_CHECK("sum", gmt_sum(n * n, u.data(), out.data(), sws.data(), s)); }};
+      const char* name[3] = {"jacobi5_resid", "jacobi5 + resid", "sum"};
+      const double bytes[3] = {8.0 * n * n, 16.0 * n * n, 8.0 * n * n};
+      int64_t seg = 0;
+      const int path = gmt_jacobi5_resid_path(xo, n, n, u.data(), ld, nullptr, 0, &seg);
+      std::printf("resid %lldx%lld  path %d, %lld rows per segment\n", (long long)n, (long long)n, path, (long long)seg);
+      Stats st[3];
+      const int order[6] = {0, 1, 2, 2, 1, 0};
+      for (int rep = 0; rep < reps; ++rep)
+        for (int k = 0; k < 6; ++k) {
+          const int v = order[k];
+          const double ms = time_ms(s, iters, variant[v]);
+          st[v].add(ms);
+          std::printf("resid %lldx%lld rep %d  %-16s %9.4f ms\n", (long long)n, (long long)n, rep, name[v], ms);
+        }
+      char shape[64];
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+      for (int v = 0; v < 3; ++v) {
+        std::printf("resid %lldx%lld summary %-16s min %9.4f  median %9.4f  max %9.4f ms\n", (long long)n, (long long)n,
+                    name[v], st[v].min(), st[v].median(), st[v].max());
+        report(name[v], v, shape, st[v].min(), bytes[v]);
+      }
+      std::printf("resid %lldx%lld  resid / (jacobi5 + resid) = %.4f   sum / resid = %.4f  (best of %d)\n", (long long)n,
+                  (long long)n, st[0].min() / st[1].min(), st[2].min() / st[0].min(), reps);
     }
   }
   if (only.find("pack") != std::string::npos) {

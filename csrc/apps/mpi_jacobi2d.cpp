@@ -26,6 +26,15 @@
 //                           (JacobiConfig::tb_shared: -1 no shared hand-off groups, 0 default,
 //                           1 / 4 groups of four strips, 2 of two; a push pass takes groups
 //                           only when asked for here)
+//   --tol=T --rtol=R        solve to tolerance (JacobiSolver::solve): sweep until the residual
+//                           r = |J(u) - u| meets r <= max(T, R * r0); n_iter is then the sweep
+//                           cap (rounded up to a multiple of E) and the timed region is one
+//                           solve() from the initial field.  Exit status 4 when the cap is hit
+//                           unconverged or the residual is not finite
+//   --norm=l2|max           the norm of r (default l2)
+//   --check-every=E         sweeps between two residual checks (default: tsteps)
+//   --lag=L                 the host decides on a check L checks behind the device (default 1,
+//                           0..8): with L >= 1 the device never idles for a check
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -131,6 +140,29 @@ int main(int argc, char** argv) {
   if (kind == comm::Kind::Auto && world == 1) kind = comm::Kind::Local;
   auto tr = comm::make_transport(comm::resolve(kind, b), MPI_COMM_WORLD, b);
 
+  // solve to tolerance: --tol / --rtol
+  const bool solve_mode = cli.has("tol") || cli.has("rtol");
+  SolveOpts so;
+  SolveResult sr;
+  double solve_ms = 0;
+  const int cap_asked = n_iter;
+  if (solve_mode) {
+    so.tol = std::atof(cli.get("tol", "0").c_str());
+    so.rtol = std::atof(cli.get("rtol", "0").c_str());
+    const std::string nm = cli.get("norm", "l2");
+    so.norm = nm == "max" ? 1 : 0;
+    so.lag = static_cast<int>(cli.geti("lag", 1));
+    so.check_every = static_cast<int>(cli.geti("check-every", 0));
+    if ((nm != "l2" && nm != "max") || so.lag < 0 || so.lag > 8 || so.check_every < 0 || n_iter < 1 ||
+        !(so.tol >= 0) || !(so.rtol >= 0) || !(so.tol > 0 || so.rtol > 0)) {
+      if (rank == 0)
+        std::printf("ERROR: solve mode needs --tol or --rtol > 0, --norm=l2|max, --lag=0..8, --check-every >= 1 "
+                    "and a sweep cap (n_iter) >= 1\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+  }
+
   double t_step = 0, resid = 0, halo_us = 0, max_diff = -1;
   bool graph = false, overlap = false, band = false, push = false, graph_sweep = false, graph_fused = false;
   size_t hbytes = 0, hmsgs = 0;
@@ -149,15 +181,34 @@ int main(int argc, char** argv) {
     hmsgs = solver.messages();
     lnx = solver.nx();
     lny = solver.ny();
-    solver.run(n_warmup);
-    solver.synchronize();
-    MPI_Barrier(MPI_COMM_WORLD);
-    const double t0 = wtime();
-    solver.run(n_iter);
-    solver.synchronize();
-    double dt = wtime() - t0;
-    MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
-    t_step = dt / (n_iter > 0 ? n_iter : 1);
+    int total_sweeps = n_warmup + n_iter;  // what --check replays
+    if (solve_mode) {
+      // the warm-up launches one pass of every kind and the residual kernel,
+      // then the field is the initial one again: the solve starts from it
+      if (so.check_every == 0) so.check_every = solver.tsteps();
+      so.max_sweeps = (n_iter + so.check_every - 1) / so.check_every * so.check_every;
+      solver.prepare(so.check_every);
+      double warm[2];
+      solver.residual_norm(warm);
+      MPI_Barrier(MPI_COMM_WORLD);
+      const double t0 = wtime();
+      sr = solver.solve(so);
+      double dt = wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      solve_ms = dt * 1e3;
+      t_step = dt / (sr.sweeps > 0 ? sr.sweeps : 1);
+      total_sweeps = sr.sweeps;
+    } else {
+      solver.run(n_warmup);
+      solver.synchronize();
+      MPI_Barrier(MPI_COMM_WORLD);
+      const double t0 = wtime();
+      solver.run(n_iter);
+      solver.synchronize();
+      double dt = wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      t_step = dt / (n_iter > 0 ? n_iter : 1);
+    }
 
     if (cli.flag("check")) {
       std::vector<double> loc(static_cast<size_t>(lnx * lny));
@@ -173,7 +224,7 @@ int main(int argc, char** argv) {
       MPI_Gatherv(loc.data(), static_cast<int>(loc.size()), MPI_DOUBLE, g.data(), counts.data(),
                   displs.data(), MPI_DOUBLE, 0, MPI_COMM_WORLD);
       if (rank == 0) {
-        std::vector<double> ref = serial_jacobi(c.ny_global, c.nx_global, n_warmup + n_iter, c.periodic, c.periodic_axes);
+        std::vector<double> ref = serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes);
         max_diff = 0;
         for (int r = 0; r < world; ++r) {
           const long long oy = all[4 * r], ox = all[4 * r + 1], ny = all[4 * r + 2], nx = all[4 * r + 3];
@@ -198,7 +249,8 @@ int main(int argc, char** argv) {
       MPI_Allreduce(&med, &halo_us, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
       halo_us *= 1e6;
     }
-    resid = solver.residual();
+    // solve mode: the deciding residual, without the extra sweep
+    resid = solve_mode ? sr.residual : solver.residual();
   }
   if (rank == 0) {
     const double pts = static_cast<double>(c.ny_global) * c.nx_global;
@@ -216,7 +268,21 @@ int main(int argc, char** argv) {
     if (c.tb_shared != 0)
       std::printf("shared    = %d (rank 0: %d strips per shared hand-off group, 0 = per-strip launch)\n", c.tb_shared,
                   sh_strips);
-    std::printf("steps     = %d (warmup %d)\n", n_iter, n_warmup);
+    if (solve_mode) {
+      std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d sweeps, lag %d\n", so.tol, so.rtol,
+                  so.norm ? "max" : "l2", so.check_every, so.lag);
+      if (so.max_sweeps != cap_asked)
+        std::printf("steps     = at most %d (%d rounded up to a multiple of %d)\n", so.max_sweeps, cap_asked,
+                    so.check_every);
+      else
+        std::printf("steps     = at most %d\n", so.max_sweeps);
+      std::printf("converged : %s%s\n", sr.converged ? "yes" : "no", sr.failed ? " (non-finite residual)" : "");
+      std::printf("sweeps    : %d (criterion met at %d, %d checks, lag %d)\n", sr.sweeps, sr.residual_sweeps, sr.checks,
+                  so.lag);
+      std::printf("TIME solve: %0.6f ms\n", solve_ms);
+    } else {
+      std::printf("steps     = %d (warmup %d)\n", n_iter, n_warmup);
+    }
     std::printf("TIME step : %0.6f ms\n", t_step * 1e3);
     std::printf("MLUPS     : %0.1f (per GPU %0.1f, %0.1f GB/s per GPU at 16 B/pt)\n", mlups,
                 mlups / world, 16.0 * pts / world / t_step / 1e9);
@@ -231,9 +297,13 @@ int main(int argc, char** argv) {
         .add("overlap", overlap).add("band_first", band).add("push", push).add("shared_strips", sh_strips).add("graph", graph).add("graph_fused", graph_fused).add("tblock", c.tblock).add("steps", n_iter).add("ms_per_step", t_step * 1e3)
         .add("MLUPS", mlups).add("halo_us", halo_us).add("halo_bytes", hbytes).add("residual", resid)
         .add("check_max_diff", max_diff);
+    if (solve_mode)
+      j.add("converged", sr.converged != 0).add("sweeps", sr.sweeps).add("residual_sweeps", sr.residual_sweeps)
+          .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
     j.append_to(cli.get("json", ""));
   }
   tr.reset();
   MPI_Finalize();
-  return max_diff >= 1e-10 ? 3 : EXIT_SUCCESS;
+  if (max_diff >= 1e-10) return 3;
+  return solve_mode && (!sr.converged || sr.failed) ? 4 : EXIT_SUCCESS;
 }

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <string>
 #include <memory>
+#include <stdexcept>
 #include <vector>
 
 #include <unistd.h>
@@ -189,6 +190,31 @@ int gmt_engine_jacobi_sync(void* p) {
   return 0;
 }
 double gmt_engine_jacobi_residual(void* p) { return static_cast<Handle*>(p)->s->residual(); }
+int gmt_engine_jacobi_residual_norm(void* p, double out[2]) {
+  if (!p || !out) return 1;
+  gmt::watchdog_kick("engine: jacobi residual norm");
+  static_cast<Handle*>(p)->s->residual_norm(out);
+  return 0;
+}
+int gmt_engine_jacobi_solve(void* p, const gmt_engine_solve_opts* o, gmt_engine_solve_result* out) {
+  if (!p || !o || !out) return 1;
+  gmt::watchdog_kick("engine: jacobi solve");
+  gmt::SolveOpts so;
+  so.tol = o->tol;
+  so.rtol = o->rtol;
+  so.norm = o->norm;
+  so.max_sweeps = o->max_sweeps;
+  so.check_every = o->check_every;
+  so.lag = o->lag;
+  gmt::SolveResult r;
+  try {
+    r = static_cast<Handle*>(p)->s->solve(so);
+  } catch (const std::invalid_argument&) {
+    return 1;
+  }
+  *out = {r.converged, r.sweeps, r.checks, r.residual_sweeps, r.residual, r.residual_max, r.r0, r.failed};
+  return 0;
+}
 int gmt_engine_jacobi_exchange(void* p) {
   gmt::watchdog_kick("engine: halo exchange");
   static_cast<Handle*>(p)->s->exchange_only();

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -323,6 +324,8 @@ JacobiSolver::~JacobiSolver() {
   if (ev_band_) gmt_rt_event_destroy(ev_band_);
   halo_[0].reset();
   halo_[1].reset();
+  for (auto e : rn_ev_)
+    if (e) gmt_rt_event_destroy(e);
   gmt_rt_stream_destroy(cs_);
   if (sb_) gmt_rt_stream_destroy(sb_);
   gmt_rt_stream_destroy(s_);
@@ -910,6 +913,81 @@ double JacobiSolver::residual() {
   GMT_CHECK("resid sync", gmt_rt_stream_synchronize(s_));
   parity_ ^= 1;
   return std::sqrt(r);
+}
+
+// The read-only residual of the current field, all-reduced, left in rn_dev_:
+// everything stream-ordered on s_, nothing waits.  The sum is followed by a
+// max over both values: whatever order a transport adds in, every rank then
+// holds the same two doubles and takes the same decision.
+void JacobiSolver::enqueue_residual() {
+  if (!rn_dev_.data()) {
+    rn_ws_ = Buffer<double>(static_cast<size_t>(gmt_jacobi5_resid_workspace(nx_, ny_)), GMT_SPACE_DEVICE);
+    rn_dev_ = Buffer<double>(2, GMT_SPACE_DEVICE);
+    rn_ring_ = Buffer<double>(2 * (kMaxLag + 1), GMT_SPACE_PINNED);
+    for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
+  }
+  if (!fresh_[parity_]) exchange_now(parity_);
+  GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, nullptr, 0, kC0, 0.0,
+                                                 rn_dev_.data(), rn_ws_.data(), s_));
+  t_.allreduce_sum(rn_dev_.data(), 1, s_);
+  t_.allreduce_max(rn_dev_.data(), 2, s_);
+}
+
+void JacobiSolver::residual_norm(double out[2]) {
+  enqueue_residual();
+  GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data(), rn_dev_.data(), 2 * sizeof(double), s_));
+  GMT_CHECK("resid sync", gmt_rt_stream_synchronize(s_));
+  out[0] = std::sqrt(rn_ring_[0]);
+  out[1] = rn_ring_[1];
+}
+
+SolveResult JacobiSolver::solve(const SolveOpts& o) {
+  const int every = o.check_every == 0 ? ks_ : o.check_every;
+  if (every < 1 || o.max_sweeps < 1 || o.max_sweeps % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
+      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !(o.tol > 0.0 || o.rtol > 0.0) ||
+      !std::isfinite(o.tol) || !std::isfinite(o.rtol))
+    throw std::invalid_argument("JacobiSolver::solve: max_sweeps must be a positive multiple of check_every >= 1, "
+                                "0 <= lag <= 8, norm 0 or 1, and tol or rtol positive");
+  const int slots = o.lag + 1, last = o.max_sweeps / every;  // checks 0..last
+  SolveResult res;
+  int decided = 0;  // checks decided so far
+  bool stop = false;
+  // decide on check i (its event has been recorded): every rank reads the
+  // same all-reduced pair, so every rank stops at the same check
+  auto decide = [&](int i) {
+    GMT_CHECK("solve check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
+    watchdog_kick("jacobi solve check");
+    const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
+    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
+    res.residual_sweeps = i * every;
+    res.residual = r;
+    res.residual_max = mx;
+    if (i == 0) res.r0 = r;
+    if (!std::isfinite(sum) || !std::isfinite(mx)) {
+      res.failed = 1;
+      stop = true;
+    } else if (r <= std::max(o.tol, o.rtol * res.r0)) {
+      res.converged = 1;
+      stop = true;
+    }
+  };
+  for (int i = 0; i <= last && !stop; ++i) {
+    if (i > 0) {
+      run(every);
+      res.sweeps += every;
+    }
+    enqueue_residual();
+    GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), rn_dev_.data(),
+                                               2 * sizeof(double), s_));
+    GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
+    res.checks = i + 1;
+    if (i >= o.lag) decide(decided++);
+  }
+  // drain the outstanding checks in order (the cap, or a stop with lag > 0:
+  // the later checks' sweeps have run, an earlier check still decides)
+  while (!stop && decided < res.checks) decide(decided++);
+  synchronize();
+  return res;
 }
 
 void JacobiSolver::exchange_only() {

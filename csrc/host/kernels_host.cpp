@@ -267,6 +267,37 @@ int gmt_jacobi5(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u,
   return 0;
 }
 
+// the read-only residual (jacobi5_resid.hip); this file is built with
+// -ffp-contract=off, as the device cell is
+int64_t gmt_jacobi5_resid_workspace(int64_t, int64_t) { return 2; }
+
+int gmt_jacobi5_resid_path(int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
+                           int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_jacobi5_resid(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld,
+                      const double* f, int64_t ldf, double c0, double c1, double* out, double*, void*) {
+  if (!out) return 1;
+  double acc = 0.0, m = 0.0;
+  if (nx > 0 && ny > 0) {
+    if (!u || x0 < 1 || y0 < 1 || ld < x0 + nx + 1) return 1;
+    for (int64_t y = y0; y < y0 + ny; ++y)
+      for (int64_t x = x0; x < x0 + nx; ++x) {
+        const double* p = u + y * ld + x;
+        double o = c0 * ((p[-1] + p[1]) + (p[-ld] + p[ld]));
+        if (f) o += c1 * f[y * ldf + x];
+        const double d = o - p[0];
+        acc += d * d;
+        m = std::max(m, std::isnan(d) ? HUGE_VAL : std::fabs(d));
+      }
+  }
+  out[0] = acc;
+  out[1] = m;
+  return 0;
+}
+
 int gmt_jacobi5_rects(int n_rect, const int64_t* r, const double* u, double* un, int64_t ld,
                       const double* f, int64_t ldf, double c0, double c1, void*) {
   if (n_rect > 4) return 1;

@@ -56,6 +56,27 @@ int gmt_engine_jacobi_run(void* h, int steps); /* enqueue `steps` steps */
 int gmt_engine_jacobi_sync(void* h);
 double gmt_engine_jacobi_residual(void* h);
 int gmt_engine_jacobi_exchange(void* h); /* one blocking halo exchange */
+/* {sqrt(sum over ranks of d^2), max over ranks of |d|} of d = J(u) - u on the
+ * current field; read-only: the field and the sweep count are unchanged
+ * (JacobiSolver::residual_norm).  Collective. */
+int gmt_engine_jacobi_residual_norm(void* h, double out[2]);
+/* Solve to tolerance (JacobiSolver::solve, gmt/jacobi.hpp SolveOpts /
+ * SolveResult): r <= max(tol, rtol * r0) in the chosen norm, checked every
+ * check_every sweeps, the host deciding `lag` checks behind the device. */
+typedef struct gmt_engine_solve_opts {
+  double tol, rtol; /* at least one positive */
+  int norm;         /* 0 L2, 1 max */
+  int max_sweeps;   /* a positive multiple of check_every */
+  int check_every;  /* 0 = tsteps */
+  int lag;          /* 0..8 */
+} gmt_engine_solve_opts;
+typedef struct gmt_engine_solve_result {
+  int converged, sweeps, checks, residual_sweeps;
+  double residual, residual_max, r0;
+  int failed; /* 1: a non-finite residual stopped the solve */
+} gmt_engine_solve_result;
+/* 0, or 1 on invalid options (nothing enqueued).  Collective. */
+int gmt_engine_jacobi_solve(void* h, const gmt_engine_solve_opts* opts, gmt_engine_solve_result* out);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,
  * overlap_auto ns per pass with overlap, without (0 if not tuned), exact arithmetic in use,
  * band-first passes, inline halo exchange in use */

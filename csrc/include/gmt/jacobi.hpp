@@ -98,6 +98,27 @@ struct JacobiConfig {
   int tb_shared = 0;
 };
 
+// JacobiSolver::solve: sweep until the residual d = J(u) - u of the current
+// field meets r <= max(tol, rtol * r0) in the chosen norm (r0: the residual of
+// the field the solve starts from), or max_sweeps have run.
+struct SolveOpts {
+  double tol = 0.0, rtol = 0.0;  // at least one must be positive
+  int norm = 0;                  // 0: L2 (sqrt of the global sum of d^2), 1: max |d|
+  int max_sweeps = 0;            // the cap: a positive multiple of check_every
+  int check_every = 0;           // sweeps between two checks (0 = tsteps)
+  int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
+};
+struct SolveResult {
+  int converged = 0;        // the criterion was met
+  int sweeps = 0;           // sweeps advanced: residual_sweeps + lag * check_every unless the cap came first
+  int checks = 0;           // checks enqueued
+  int residual_sweeps = 0;  // sweep count of the deciding check
+  double residual = 0.0;    // its residual in the chosen norm,
+  double residual_max = 0.0;  // its max |d|,
+  double r0 = 0.0;          // and the residual before any sweep (chosen norm)
+  int failed = 0;           // 1: a non-finite residual stopped the solve
+};
+
 class JacobiSolver {
  public:
   JacobiSolver(comm::Transport& t, const JacobiConfig& c);
@@ -112,6 +133,18 @@ class JacobiSolver {
   void synchronize();
   // sqrt(global sum (u_{k+1} - u_k)^2) of one extra sweep (advances the solution)
   double residual();
+  // {sqrt(global sum d^2), global max |d|} of d = J(u) - u on the current
+  // field, read-only (gmt_jacobi5_resid): the field, its parity and the sweep
+  // count are unchanged.  A halo exchange it has to make is the next pass's
+  // (fresh_).  Collective; synchronises the compute stream.
+  void residual_norm(double out[2]);
+  // Convergence-driven run: check i (the residual kernel, its two all-reduces,
+  // an async copy into a page-locked ring, an event) is enqueued after
+  // i * check_every sweeps, run(check_every) between checks, and the host
+  // waits for the event of check i - lag only: with lag >= 1 the device never
+  // idles for a check.  Every rank decides on the all-reduced values of the
+  // same check.  Throws std::invalid_argument on bad options (nothing enqueued).
+  SolveResult solve(const SolveOpts& o);
   // one blocking halo exchange of the current field (latency measurements);
   // ordered after every pass already enqueued
   void exchange_only();
@@ -192,6 +225,7 @@ class JacobiSolver {
   int halo_mask() const;
   void split_cus();
   void setup_push();
+  void enqueue_residual();  // {sum d^2, max |d|} over every rank into rn_dev_, stream-ordered on s_
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
   void push_pass(int parity, int k);   // the pass launch alone
@@ -208,6 +242,11 @@ class JacobiSolver {
   Buffer<double> buf_[2];
   std::unique_ptr<Halo2D> halo_[2];
   Buffer<double> resid_ws_;
+  // residual_norm / solve: the kernel's workspace, its device result and the
+  // page-locked ring of check results with one event per slot (made on first use)
+  static constexpr int kMaxLag = 8;
+  Buffer<double> rn_ws_, rn_dev_, rn_ring_;
+  gmt_event_t rn_ev_[kMaxLag + 1] = {};
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values
   gmt_stream_t s_ = nullptr, cs_ = nullptr;

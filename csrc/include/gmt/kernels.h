@@ -39,9 +39,11 @@ int gmt_stencil5_2d(int dim, int64_t nx_out, int64_t ny_out, const double* coef5
                     int64_t ld_out, void* stream);
 /* Which kernel a launcher picks (tests assert the path a case ran): the
  * one-element-per-lane fallback, the pair-per-thread kernels (stencil5_pt,
- * jacobi5_pt), the dim-1 register-window walk, the dim-1 LDS-DMA pipeline.
+ * jacobi5_pt), the dim-1 register-window walk, the dim-1 LDS-DMA pipeline,
+ * the row walk of the read-only Jacobi residual.
  * The CPU backend has no kernels to pick from and answers GMT_PATH_NONE. */
-enum { GMT_PATH_NONE = 0, GMT_PATH_SCALAR = 1, GMT_PATH_PT = 2, GMT_PATH_D1_WIN = 3, GMT_PATH_D1_DMA = 4 };
+enum { GMT_PATH_NONE = 0, GMT_PATH_SCALAR = 1, GMT_PATH_PT = 2, GMT_PATH_D1_WIN = 3, GMT_PATH_D1_DMA = 4,
+       GMT_PATH_ROW_WALK = 5 };
 /* the kernel gmt_stencil5_2d would launch for these arguments (no launch);
    *seg_rows (may be NULL) gets the rows per segment of the dim-1 kernels, 0 otherwise */
 int gmt_stencil5_2d_path(int dim, int64_t nx_out, int64_t ny_out, const double* in, int64_t ld_in,
@@ -180,6 +182,22 @@ int gmt_jacobi5_path(int64_t x0, const double* u, const double* un, int64_t ld, 
 int gmt_jacobi5_rects(int n_rect, const int64_t* rects, const double* u, double* un,
                       int64_t ld, const double* f, int64_t ldf, double c0, double c1,
                       void* stream);
+/* ---- Read-only residual of that sweep (csrc/kernels/jacobi5_resid.hip), one
+ *      HBM read pass, u is never written.  With
+ *        d = c0*((u[y][x-1]+u[y][x+1]) + (u[y-1][x]+u[y+1][x])) [+ c1*f[y][x]] - u[y][x]
+ *      over the region (evaluated without contraction): out[0] = sum d^2 (not
+ *      square-rooted, so partial results can be all-reduced), out[1] = max |d|
+ *      with a NaN d counted as +inf.  Deterministic summation order; an empty
+ *      region gives {0, 0}.  `workspace` must hold
+ *      gmt_jacobi5_resid_workspace(nx, ny) doubles. */
+int64_t gmt_jacobi5_resid_workspace(int64_t nx, int64_t ny);
+int gmt_jacobi5_resid(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld,
+                      const double* f, int64_t ldf, double c0, double c1,
+                      double* out /* 2 doubles */, double* workspace, void* stream);
+/* GMT_PATH_ROW_WALK or GMT_PATH_SCALAR: the kernel the call would launch, nothing launched;
+ * *seg_rows (may be NULL) = rows per segment of the row walk, 0 otherwise */
+int gmt_jacobi5_resid_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f,
+                           int64_t ldf, int64_t* seg_rows);
 /* ---- Temporal-blocking Jacobi (csrc/kernels/jacobi5tb.hip): `sweeps` fused
  *      Laplace sweeps per memory pass, un = J^sweeps(u), on up to 8 output
  *      rects {x0, nx, y0, ny} (absolute array coordinates, x0 >= sweeps,

@@ -70,6 +70,20 @@ __device__ __forceinline__ double block_sum(double v) {
   return t;
 }
 
+// Max over a 256-thread block; result valid in every thread.
+__device__ __forceinline__ double block_max(double v) {
+  __shared__ double s_part[kBlock / kWave];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) s_part[threadIdx.x / kWave] = v;
+  __syncthreads();
+  double t = s_part[0];
+#pragma unroll
+  for (int i = 1; i < kBlock / kWave; ++i) t = fmax(t, s_part[i]);
+  __syncthreads();
+  return t;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline unsigned grid_1d(int64_t nblocks) { return static_cast<unsigned>(nblocks); }

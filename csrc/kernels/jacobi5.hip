@@ -16,6 +16,7 @@
 // csrc/bench/variant_bench.hip.  jacobi5_scalar: odd alignment and the
 // frame rects.  Multi-sweep passes: jacobi5tb.hip.
 #include "common.hpp"
+#include "reduce_partials.hpp"
 #include "gmt/kernels.h"
 
 namespace gmt {
@@ -95,27 +96,6 @@ __global__ __launch_bounds__(kBlock) void jacobi5_scalar(Rects rs, const double*
   }
 }
 
-// Deterministic reduction of per-block partials: level 1 sums contiguous
-// chunks with up to kL2 blocks, level 2 (one block) sums those.  The
-// summation order depends only on n, so results are run-to-run identical.
-constexpr int64_t kL2 = 1024;
-__global__ __launch_bounds__(kBlock) void sum_chunks(const double* __restrict__ partial, int64_t n,
-                                                     int64_t chunk, double* __restrict__ out) {
-  const int64_t lo = blockIdx.x * chunk, hi = (lo + chunk) < n ? (lo + chunk) : n;
-  double acc = 0.0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) acc += partial[i];
-  acc = block_sum(acc);
-  if (threadIdx.x == 0) out[blockIdx.x] = acc;
-}
-
-__global__ __launch_bounds__(kBlock) void sum_partials(const double* __restrict__ partial,
-                                                       int64_t n, double* __restrict__ out) {
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += kBlock) acc += partial[i];
-  acc = block_sum(acc);
-  if (threadIdx.x == 0) out[0] = acc;
-}
-
 static Rects make_rects(int n, const int64_t* rects) {
   Rects rs{};
   rs.n = 0;
@@ -148,18 +128,6 @@ extern "C" int64_t gmt_jacobi_resid_workspace(int64_t nx, int64_t ny) {
 }
 
 namespace gmt {
-static void reduce_partials(const double* partial, int64_t nb, double* out, hipStream_t s) {
-  if (nb <= 4 * kBlock) {
-    sum_partials<<<1, kBlock, 0, s>>>(partial, nb, out);
-    return;
-  }
-  const int64_t nb2 = nb < kL2 ? nb : kL2;
-  const int64_t chunk = (nb + nb2 - 1) / nb2;
-  const int64_t used = (nb + chunk - 1) / chunk;
-  double* l2 = const_cast<double*>(partial) + nb;
-  sum_chunks<<<grid_1d(used), kBlock, 0, s>>>(partial, nb, chunk, l2);
-  sum_partials<<<1, kBlock, 0, s>>>(l2, used, out);
-}
 // The one dispatch decision of gmt_jacobi5 (and the answer of
 // gmt_jacobi5_path): pairs per thread need 16-B aligned rows and an even
 // first column.
@@ -208,7 +176,7 @@ extern "C" int gmt_jacobi5(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const
     else { if (want_r) GMT_J3(false, true); else GMT_J3(false, false); }
 #undef GMT_J3
   }
-  if (want_r) reduce_partials(partial, nb, resid, s);
+  if (want_r) reduce_partials<0>(partial, nb, resid, s);
   GMT_RET_LAUNCH();
 }
 

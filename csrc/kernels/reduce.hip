@@ -188,19 +188,6 @@ __global__ __launch_bounds__(kBlock) void slices_kernel(int op, int64_t n, int n
 
 // ---------------- max |z| over a 2-D region (the engine's exactness guard on
 // a measured field bound); same tiles and workspace as diff_sq
-__device__ __forceinline__ double block_max(double v) {
-  __shared__ double s_part[kBlock / kWave];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, kWave));
-  if ((threadIdx.x & (kWave - 1)) == 0) s_part[threadIdx.x / kWave] = v;
-  __syncthreads();
-  double t = s_part[0];
-#pragma unroll
-  for (int i = 1; i < kBlock / kWave; ++i) t = fmax(t, s_part[i]);
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(kBlock) void absmax_pass1(int64_t nx, int64_t ny, const double* __restrict__ z,
                                                        int64_t ld, double* __restrict__ ws, int64_t nch) {
   const int64_t blk = blockIdx.x;
@@ -472,7 +459,7 @@ extern "C" const char* gmt_error_string(int err) {
 extern "C" int gmt_device_synchronize(void) { return static_cast<int>(hipDeviceSynchronize()); }
 
 extern "C" const char* gmt_build_info(void) {
-  return "libgmt gfx950 (CDNA4) kernels: daxpy, stencil5 1d/2d (dim 1: LDS-DMA pipeline), jacobi5, "
+  return "libgmt gfx950 (CDNA4) kernels: daxpy, stencil5 1d/2d (dim 1: LDS-DMA pipeline), jacobi5, jacobi5_resid, "
          "jacobi5tb (1-20 fused sweeps, 4 columns per lane), ipc_exchange, signal_wait, "
          "copy2d_batched, sum_axis, sum, diff_sq, diff_bits, abs_max, fill_poly; built " __DATE__ " " __TIME__;
 }

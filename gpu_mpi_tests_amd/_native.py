@@ -99,6 +99,12 @@ _SIGS = {
         c_int,
         [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_vp],
     ),
+    "gmt_jacobi5_resid_workspace": (c_i64, [c_i64, c_i64]),
+    "gmt_jacobi5_resid": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_vp, c_vp],
+    ),
+    "gmt_jacobi5_resid_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_jacobi5_rects": (
         c_int,
         [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp],

@@ -51,6 +51,23 @@ class EngineOpts(ctypes.Structure):
                  "calibrate")] + [("seed", ctypes.c_int64), ("push", ctypes.c_int), ("shared", ctypes.c_int)]
 
 
+class SolveOpts(ctypes.Structure):
+    """gmt_engine_solve_opts (csrc/include/gmt/engine.h)."""
+    _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
+                ("max_sweeps", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int)]
+
+
+class SolveResult(ctypes.Structure):
+    """gmt_engine_solve_result (csrc/include/gmt/engine.h)."""
+    _fields_ = [("converged", ctypes.c_int), ("sweeps", ctypes.c_int), ("checks", ctypes.c_int),
+                ("residual_sweeps", ctypes.c_int), ("residual", ctypes.c_double),
+                ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("failed", ctypes.c_int)]
+
+
+NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
+MAX_LAG = 8
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -94,6 +111,10 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_run.restype = c_int
     lib.gmt_engine_jacobi_residual.argtypes = [vp]
     lib.gmt_engine_jacobi_residual.restype = ctypes.c_double
+    lib.gmt_engine_jacobi_residual_norm.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    lib.gmt_engine_jacobi_residual_norm.restype = c_int
+    lib.gmt_engine_jacobi_solve.argtypes = [vp, ctypes.POINTER(SolveOpts), ctypes.POINTER(SolveResult)]
+    lib.gmt_engine_jacobi_solve.restype = c_int
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
     lib.gmt_engine_jacobi_info.restype = c_int
     lib.gmt_engine_jacobi_graphs.argtypes = [vp]
@@ -410,6 +431,46 @@ class NativeJacobi:
 
     def residual(self) -> float:
         return float(self.lib.gmt_engine_jacobi_residual(self.h))
+
+    def residual_norm(self) -> tuple[float, float]:
+        """(L2, max) norm of d = J(u) - u on the current field over every rank,
+        from the read-only residual kernel: unlike :meth:`residual` the field
+        and the sweep count are unchanged.  Collective."""
+        out = (ctypes.c_double * 2)()
+        if self.lib.gmt_engine_jacobi_residual_norm(self.h, out):
+            raise EngineError("gmt_engine_jacobi_residual_norm failed")
+        return float(out[0]), float(out[1])
+
+    def solve(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_sweeps: int = 0,
+              check_every: int = 0, lag: int = 1) -> dict:
+        """Sweep until the residual meets ``r <= max(tol, rtol * r0)`` in
+        ``norm`` ("l2" or "max"; r0: the residual before any sweep) or
+        ``max_sweeps`` have run (JacobiSolver::solve).  The residual is checked
+        every ``check_every`` sweeps (0 = tsteps) and the host decides ``lag``
+        checks behind the device, so with lag >= 1 the passes keep running
+        back to back.  Returns the fields of SolveResult: ``converged``,
+        ``sweeps`` (advanced: ``residual_sweeps + lag * check_every`` unless
+        the cap came first), ``checks``, ``residual_sweeps`` (the deciding
+        check's), ``residual``, ``residual_max``, ``r0``, ``failed`` (a
+        non-finite residual).  Identical on every rank.  Collective."""
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
+        every = int(check_every) if check_every else self.tsteps
+        if isinstance(lag, bool) or not 0 <= int(lag) <= MAX_LAG:
+            raise ValueError(f"lag must be 0..{MAX_LAG}, got {lag!r}")
+        if every < 1:
+            raise ValueError(f"check_every must be >= 1 (0 = tsteps), got {check_every!r}")
+        if int(max_sweeps) < 1 or int(max_sweeps) % every:
+            raise ValueError(f"max_sweeps must be a positive multiple of check_every ({every}), got {max_sweeps!r}")
+        tol, rtol = float(tol), float(rtol)
+        if not (np.isfinite(tol) and np.isfinite(rtol)) or tol < 0 or rtol < 0 or not (tol > 0 or rtol > 0):
+            raise ValueError("tol and rtol must be finite and >= 0, and at least one positive")
+        o = SolveOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_sweeps=int(max_sweeps), check_every=every,
+                      lag=int(lag))
+        r = SolveResult()
+        if self.lib.gmt_engine_jacobi_solve(self.h, ctypes.byref(o), ctypes.byref(r)):
+            raise ValueError("gmt_engine_jacobi_solve rejected its options")
+        return {n: getattr(r, n) for n, _ in SolveResult._fields_}
 
     def interior(self) -> np.ndarray:
         out = np.empty((self.ny, self.nx), dtype=np.float64)

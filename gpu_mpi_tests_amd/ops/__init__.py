@@ -4,7 +4,8 @@ Kernel inventory (SURVEY.md §2.3): K1/K2 ``daxpy``; K3 ``stencil5_1d``;
 K4/K5/K11 ``stencil5_2d`` (and its ``stencil5_2d_edges`` /
 ``stencil5_2d_interior`` split for overlapped steps); K6/K7/K8 ``copy2d_batched`` (halo pack/unpack);
 K9 ``sum_axis``; K10/K12 ``diff_sq``/``diff_norm``; analytic ``fill_poly``;
-and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep)
+and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
+its read-only residual ``jacobi5_resid``
 and ``jacobi5tb`` (K fused sweeps per memory pass).
 """
 from .kernels import (  # noqa: F401
@@ -20,10 +21,13 @@ from .kernels import (  # noqa: F401
     PATH_D1_WIN,
     PATH_NONE,
     PATH_PT,
+    PATH_ROW_WALK,
     PATH_SCALAR,
     jacobi5,
     jacobi5_path,
     jacobi5_rects,
+    jacobi5_resid,
+    jacobi5_resid_path,
     jacobi5xk,
     jacobi5tb,
     jacobi5tb_plan,

@@ -160,7 +160,7 @@ def stencil5_2d_interior(inp: torch.Tensor, dim: int, out: torch.Tensor, sides: 
 
 
 # gmt/kernels.h GMT_PATH_*: the kernel a launcher picks
-PATH_NONE, PATH_SCALAR, PATH_PT, PATH_D1_WIN, PATH_D1_DMA = range(5)
+PATH_NONE, PATH_SCALAR, PATH_PT, PATH_D1_WIN, PATH_D1_DMA, PATH_ROW_WALK = range(6)
 
 
 def stencil5_2d_path(inp: torch.Tensor, dim: int, out: torch.Tensor) -> tuple[int, int]:
@@ -380,6 +380,42 @@ def jacobi5(u: torch.Tensor, un: torch.Tensor, region: tuple[int, int, int, int]
                                 f.stride(0) if f is not None else 0, float(c0), float(c1), rp,
                                 _stream(u)), "gmt_jacobi5")
     return r[0] if resid else None
+
+
+def jacobi5_resid(u: torch.Tensor, region: tuple[int, int, int, int], f: torch.Tensor | None = None,
+                  c0: float = 0.25, c1: float = 0.0) -> torch.Tensor:
+    """Read-only residual of the Jacobi update over ``region = (x0, nx, y0, ny)``
+    (gmt_jacobi5_resid; ``u`` is not written): the 2-element fp64 tensor
+    ``(sum d^2, max |d|)`` on ``u``'s device, with
+    ``d = c0*((W + E) + (N + S)) [+ c1*f] - u`` and a NaN ``d`` counted as
+    ``+inf`` in the max."""
+    _check2d(u, "jacobi5_resid.u")
+    if f is not None:
+        _check2d(f, "jacobi5_resid.f")
+    x0, nx, y0, ny = (int(v) for v in region)
+    if not _is_dev(u):
+        return ref.jacobi5_resid(u, x0, nx, y0, ny, f, c0, c1)
+    L = _native.lib()
+    ws = torch.empty(max(2, L.gmt_jacobi5_resid_workspace(nx, ny)), dtype=torch.float64, device=u.device)
+    out = torch.empty(2, dtype=torch.float64, device=u.device)
+    _native.check(L.gmt_jacobi5_resid(x0, nx, y0, ny, u.data_ptr(), u.stride(0),
+                                      f.data_ptr() if f is not None else 0,
+                                      f.stride(0) if f is not None else 0, float(c0), float(c1),
+                                      out.data_ptr(), ws.data_ptr(), _stream(u)), "gmt_jacobi5_resid")
+    return out
+
+
+def jacobi5_resid_path(u: torch.Tensor, region: tuple[int, int, int, int],
+                       f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`jacobi5_resid` would launch (gmt_jacobi5_resid_path, no
+    launch): ``(PATH_ROW_WALK or PATH_SCALAR, rows per segment of the row walk)``."""
+    x0, nx, _, ny = (int(v) for v in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_jacobi5_resid_path(x0, nx, ny, u.data_ptr(), u.stride(0),
+                                                f.data_ptr() if f is not None else 0,
+                                                f.stride(0) if f is not None else 0,
+                                                ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
 
 
 def jacobi5_rects(u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],

@@ -89,6 +89,20 @@ def jacobi5(u: torch.Tensor, un: torch.Tensor, x0: int, nx: int, y0: int, ny: in
     return (d * d).sum()
 
 
+def jacobi5_resid(u: torch.Tensor, x0: int, nx: int, y0: int, ny: int, f: torch.Tensor | None = None,
+                  c0: float = 0.25, c1: float = 0.0) -> torch.Tensor:
+    """(sum d^2, max |d| with NaN as +inf) of the Jacobi update over the region; u is not written."""
+    if nx <= 0 or ny <= 0:
+        return torch.zeros(2, dtype=u.dtype, device=u.device)
+    ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+    o = c0 * ((u[ys, x0 - 1 : x0 - 1 + nx] + u[ys, x0 + 1 : x0 + 1 + nx])
+              + (u[y0 - 1 : y0 - 1 + ny, xs] + u[y0 + 1 : y0 + 1 + ny, xs]))
+    if f is not None:
+        o = o + c1 * f[ys, xs]
+    d = o - u[ys, xs]
+    return torch.stack(((d * d).sum(), d.abs().nan_to_num(nan=float("inf")).max()))
+
+
 def jacobi5xk(k: int, u: torch.Tensor, un: torch.Tensor, rects, dom, halo_mask: int = 0) -> None:
     """fp64 reference of k fused Laplace sweeps with the ghost-side rule of
     csrc/kernels/jacobi5tb.hip: a ring cell outside ``dom`` gets an
