@@ -155,7 +155,8 @@ int gmt_slices_reduce(int op, int64_t n, int nslices, const double* in, double* 
   if (n < 0 || nslices < 1 || (op != 0 && op != 1)) return 1;
   for (int64_t i = 0; i < n; ++i) {
     double v = in[i];
-    for (int r = 1; r < nslices; ++r) v = op == 0 ? v + in[r * n + i] : std::max(v, in[r * n + i]);
+    // max = fmax, as the GPU kernel: a NaN operand is ignored unless every slice holds NaN
+    for (int r = 1; r < nslices; ++r) v = op == 0 ? v + in[r * n + i] : std::fmax(v, in[r * n + i]);
     out[i] = v;
   }
   return 0;
@@ -508,8 +509,13 @@ int gmt_ipc_plan_init(gmt_ipc_plan* p, int n_send, const gmt_ipc_chan* sends, in
   auto* c = static_cast<gmt_ipc_chan*>(p->table);
   for (int k = 0; k < n_send + n_recv; ++k) {
     c[k] = k < n_send ? sends[k] : recvs[k - n_send];
-    if (c[k].bytes < 0 || c[k].src_run < 0 || c[k].dst_run < 0) return 1;
-    if (c[k].src_run && c[k].dst_run && c[k].src_run != c[k].dst_run) return 1;
+    // the GPU launcher's rules (csrc/kernels/ipc.hip): a plan is valid on both backends or on neither
+    auto bad_side = [&](int64_t run, int64_t ld) {
+      return run < 0 || (run > 0 && (ld < run || c[k].bytes % run != 0 || c[k].bytes > 0xffffffffll));
+    };
+    if (c[k].bytes < 0 || bad_side(c[k].src_run, c[k].src_ld) || bad_side(c[k].dst_run, c[k].dst_ld) ||
+        (c[k].src_run != 0 && c[k].dst_run != 0))
+      return 1;
   }
   p->n_send = n_send;
   p->n_recv = n_recv;
@@ -548,7 +554,7 @@ int gmt_ipc_exchange(const gmt_ipc_plan* p, void*) {
       const char* s = static_cast<const char*>(c.src) + (e & 1) * c.src_stride;
       if (c.src_run == 0 && c.dst_run == 0) {
         std::memcpy(d, s, static_cast<size_t>(c.bytes));
-      } else {  // one side strided: run by run (both runs equal the face's width)
+      } else {  // one side strided (gmt_ipc_plan_init refuses both): run by run, whole runs
         const int64_t run = c.src_run ? c.src_run : c.dst_run;
         for (int64_t o = 0, r = 0; o < c.bytes; o += run, ++r)
           std::memcpy(d + (c.dst_run ? r * c.dst_ld : o), s + (c.src_run ? r * c.src_ld : o),

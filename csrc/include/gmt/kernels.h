@@ -126,7 +126,11 @@ int gmt_sum(int64_t n, const double* x, double* out, double* workspace, void* st
 
 /* ---- out[i] = sum (op 0) or max (op 1) over r = 0..nslices-1 of
  *      in[r*n + i], in rank order (an all-gather + this = a deterministic
- *      all-reduce; out may alias slice 0 of in only if it is in[0..n)) */
+ *      all-reduce; out may alias slice 0 of in only if it is in[0..n)).
+ *      The sum is the IEEE additions acc = in[i]; acc += in[r*n + i] (inf and
+ *      NaN propagate); the max is fmax in the same order on both backends: a
+ *      NaN operand is ignored, out[i] is NaN only if every slice holds NaN.
+ *      n == 0 does nothing; op > 1, n < 0 or nslices < 1 is refused. */
 int gmt_slices_reduce(int op, int64_t n, int nslices, const double* in, double* out, void* stream);
 
 /* ---- max over the nx x ny region of |z| -> out[0]; workspace of
@@ -403,7 +407,8 @@ typedef struct gmt_ipc_chan {
   uint64_t* signal;
   /* strided side (a halo face moved in place, Transport::takes_blocks): the
      message is runs of src_run / dst_run bytes, src_ld / dst_ld bytes apart;
-     run 0 = contiguous.  The staging slot side is always contiguous. */
+     run 0 = contiguous.  The staging slot side is always contiguous: a
+     channel with src_run != 0 and dst_run != 0 is refused. */
   int64_t src_run, src_ld, dst_run, dst_ld;
 } gmt_ipc_chan;
 typedef struct gmt_ipc_plan {
@@ -416,7 +421,10 @@ typedef struct gmt_ipc_plan {
 } gmt_ipc_plan;
 int64_t gmt_ipc_table_bytes(int n_chan);
 /* Writes the channel table (synchronous copy) and the chunk counts; any
- * number of channels.  table/epoch/counters/err must be set by the caller. */
+ * number of channels.  table/epoch/counters/err must be set by the caller.
+ * Refused (non-zero, the same on both backends): a NULL table, n_send + n_recv == 0, a negative count, bytes or
+ * run; for a strided side ld < run, bytes % run != 0 or bytes > 0xffffffff
+ * (the kernel's 32-bit division); both sides strided. */
 int gmt_ipc_plan_init(gmt_ipc_plan* plan, int n_send, const gmt_ipc_chan* sends, int n_recv,
                       const gmt_ipc_chan* recvs);
 int gmt_ipc_exchange(const gmt_ipc_plan* plan, void* stream);

@@ -328,11 +328,13 @@ extern "C" int gmt_ipc_plan_init(gmt_ipc_plan* p, int n_send, const gmt_ipc_chan
   for (int k = 0; k < n; ++k) {
     c[k] = k < n_send ? sends[k] : recvs[k - n_send];
     // strided sides: whole runs, a pitch no shorter than the run, offsets
-    // that fit the kernel's 32-bit division
+    // that fit the kernel's 32-bit division; at most one side is strided
+    // (the other one is a staging slot)
     auto bad_side = [&](int64_t run, int64_t ld) {
       return run < 0 || (run > 0 && (ld < run || c[k].bytes % run != 0 || c[k].bytes > 0xffffffffll));
     };
-    if (c[k].bytes < 0 || bad_side(c[k].src_run, c[k].src_ld) || bad_side(c[k].dst_run, c[k].dst_ld)) {
+    if (c[k].bytes < 0 || bad_side(c[k].src_run, c[k].src_ld) || bad_side(c[k].dst_run, c[k].dst_ld) ||
+        (c[k].src_run != 0 && c[k].dst_run != 0)) {
       std::free(host);
       return static_cast<int>(hipErrorInvalidValue);
     }

@@ -76,7 +76,57 @@ class TbOpts(ctypes.Structure):
         ("shared", c_int),
     ]
 
+class IpcChan(ctypes.Structure):
+    """gmt_ipc_chan (csrc/include/gmt/kernels.h)."""
+    _fields_ = [
+        ("src", c_vp),
+        ("dst", c_vp),
+        ("bytes", c_i64),
+        ("src_stride", c_i64),
+        ("dst_stride", c_i64),
+        ("wait", c_vp),
+        ("signal", c_vp),
+        ("src_run", c_i64),
+        ("src_ld", c_i64),
+        ("dst_run", c_i64),
+        ("dst_ld", c_i64),
+    ]
+
+
+class IpcPlan(ctypes.Structure):
+    """gmt_ipc_plan (csrc/include/gmt/kernels.h)."""
+    _fields_ = [
+        ("table", c_vp),
+        ("epoch", c_vp),
+        ("counters", c_vp),
+        ("err", c_vp),
+        ("n_send", c_int),
+        ("n_recv", c_int),
+        ("send_chunks", c_i64),
+        ("recv_chunks", c_i64),
+    ]
+
+
+# enum gmt_space (csrc/include/gmt/rt.h)
+SPACE_HOST, SPACE_DEVICE, SPACE_PINNED, SPACE_MANAGED, SPACE_FLAGS, SPACE_PINNED_COHERENT = 0, 1, 2, 3, 4, 5
+
 _SIGS = {
+    "gmt_rt_backend": (c_int, []),
+    "gmt_rt_malloc": (c_int, [ctypes.POINTER(c_vp), ctypes.c_size_t, c_int]),
+    "gmt_rt_free": (c_int, [c_vp, c_int]),
+    "gmt_rt_memcpy": (c_int, [c_vp, c_vp, ctypes.c_size_t]),
+    "gmt_rt_memset_async": (c_int, [c_vp, c_int, ctypes.c_size_t, c_vp]),
+    "gmt_rt_stream_create": (c_int, [ctypes.POINTER(c_vp), c_int]),
+    "gmt_rt_stream_destroy": (c_int, [c_vp]),
+    "gmt_rt_stream_synchronize": (c_int, [c_vp]),
+    "gmt_rt_stream_begin_capture": (c_int, [c_vp]),
+    "gmt_rt_stream_end_capture": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "gmt_rt_graph_launch": (c_int, [c_vp, c_vp]),
+    "gmt_rt_graph_destroy": (c_int, [c_vp]),
+    "gmt_ipc_table_bytes": (c_i64, [c_int]),
+    "gmt_ipc_plan_init": (c_int, [ctypes.POINTER(IpcPlan), c_int, c_vp, c_int, c_vp]),
+    "gmt_ipc_exchange": (c_int, [ctypes.POINTER(IpcPlan), c_vp]),
+    "gmt_slices_reduce": (c_int, [c_int, c_i64, c_int, c_vp, c_vp, c_vp]),
     "gmt_daxpy": (c_int, [c_i64, c_dbl, c_vp, c_vp, c_vp]),
     "gmt_stencil5_1d": (c_int, [c_i64, c_vp, c_dbl, c_vp, c_vp, c_vp]),
     "gmt_stencil5_2d": (c_int, [c_int, c_i64, c_i64, c_vp, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp]),
@@ -135,6 +185,17 @@ class NativeError(RuntimeError):
     pass
 
 
+def bind(lib, names=None):
+    """Set the prototypes of `names` (default: every entry point) on a loaded
+    libgmt.so — this package's own, or the CPU backend a test loads by path."""
+    for name in _SIGS if names is None else names:
+        res, args = _SIGS[name]
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def _load():
     global _lib, _load_error
     with _lock:
@@ -145,12 +206,7 @@ def _load():
             # importing it here guarantees libgmt binds to the already-loaded copy.
             import torch  # noqa: F401
 
-            lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-            for name, (res, args) in _SIGS.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = lib
+            _lib = bind(ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL))
         except Exception as e:  # pragma: no cover - exercised when lib missing
             _load_error = e
 

@@ -45,23 +45,7 @@ def _need_gpu():
 
 
 def _rt():
-    L = _native.lib()
-    vp = ctypes.c_void_p
-    L.gmt_rt_malloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t, ctypes.c_int]
-    L.gmt_rt_free.argtypes = [vp, ctypes.c_int]
-    L.gmt_rt_memcpy.argtypes = [vp, vp, ctypes.c_size_t]
-    L.gmt_rt_memset_async.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, vp]
-    L.gmt_rt_stream_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-    L.gmt_rt_stream_destroy.argtypes = [vp]
-    L.gmt_rt_stream_synchronize.argtypes = [vp]
-    L.gmt_rt_stream_begin_capture.argtypes = [vp]
-    L.gmt_rt_stream_end_capture.argtypes = [vp, ctypes.POINTER(vp)]
-    L.gmt_rt_graph_launch.argtypes = [vp, vp]
-    L.gmt_rt_graph_destroy.argtypes = [vp]
-    for f in ("malloc", "free", "memcpy", "memset_async", "stream_create", "stream_destroy", "stream_synchronize",
-              "stream_begin_capture", "stream_end_capture", "graph_launch", "graph_destroy"):
-        getattr(L, "gmt_rt_" + f).restype = ctypes.c_int
-    return L
+    return _native.lib()  # the gmt_rt_* prototypes are declared with the kernels' (_native._SIGS)
 
 
 def test_push_sync_dev_kernel_eager_and_replayed():
