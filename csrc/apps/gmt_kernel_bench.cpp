@@ -13,6 +13,8 @@
 //      (gmt_stencil5_2d_edges / _interior) against the whole-field kernels
 //      --only=resid [--reps=5]: the read-only Jacobi residual (8 B/point) against
 //      the sweep with residual (16 B/point) and gmt_sum, at 8192^2 and 32768^2
+//      --only=add2d [--reps=5]: the source-block add (gmt_add2d) alternated with
+//      gmt_daxpy on the same element count (24 B/point each)
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -342,6 +344,46 @@ int main(int argc, char** argv) {
       }
       std::printf("resid %lldx%lld  resid / (jacobi5 + resid) = %.4f   sum / resid = %.4f  (best of %d)\n", (long long)n,
                   (long long)n, st[0].min() / st[1].min(), st[2].min() / st[0].min(), reps);
+    }
+  }
+  if (only.find("add2d") != std::string::npos) {
+    // --only=add2d: the add that ends a source block of the Jacobi engine
+    // (gmt_add2d, A: the engine's layout — interior at column 8, pitch padded
+    // to 64) against gmt_daxpy on the same number of elements (B: the same
+    // 24 B per element, contiguous), at 8192^2 and 32768^2, --reps=5 rounds in
+    // the order A B B A; the best of the rounds is compared.  --add2d-n=N: one size.
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    std::vector<int64_t> sizes = {8192, 32768};
+    if (cli.has("add2d-n")) sizes = {static_cast<int64_t>(cli.geti("add2d-n", 8192))};
+    for (const int64_t n : sizes) {
+      const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64;
+      Buffer<double> g(static_cast<size_t>(ld) * (n + 2), GMT_SPACE_DEVICE), u(g.size(), GMT_SPACE_DEVICE);
+      GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, u.data(), ld, s));
+      GMT_CHECK("fill", gmt_fill_poly(3, ld, n + 2, 0.0, 1e-9, 0.0, 0.0, g.data(), ld, s));
+      const std::function<void()> variant[2] = {
+          [&] { GMT_CHECK("add2d", gmt_add2d(n, n, g.data() + ld + xo, ld, u.data() + ld + xo, ld, s)); },
+          [&] { GMT_CHECK("daxpy", gmt_daxpy(n * n, 1e-3, g.data(), u.data(), s)); }};
+      const char* name[2] = {"add2d", "daxpy"};
+      std::printf("add2d %lldx%lld  path %d, pitch %lld\n", (long long)n, (long long)n,
+                  gmt_add2d_path(n, g.data() + ld + xo, ld, u.data() + ld + xo, ld), (long long)ld);
+      Stats st[2];
+      const int order[4] = {0, 1, 1, 0};
+      for (int rep = 0; rep < reps; ++rep)
+        for (int k = 0; k < 4; ++k) {
+          const int v = order[k];
+          const double ms = time_ms(s, iters, variant[v]);
+          st[v].add(ms);
+          std::printf("add2d %lldx%lld rep %d  %-8s %9.4f ms\n", (long long)n, (long long)n, rep, name[v], ms);
+        }
+      char shape[64];
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+      for (int v = 0; v < 2; ++v) {
+        std::printf("add2d %lldx%lld summary %-8s min %9.4f  median %9.4f  max %9.4f ms\n", (long long)n, (long long)n,
+                    name[v], st[v].min(), st[v].median(), st[v].max());
+        report(name[v], v, shape, st[v].min(), 24.0 * n * n);
+      }
+      std::printf("add2d %lldx%lld  add2d / daxpy = %.4f  (best of %d)\n", (long long)n, (long long)n,
+                  st[0].min() / st[1].min(), reps);
     }
   }
   if (only.find("pack") != std::string::npos) {

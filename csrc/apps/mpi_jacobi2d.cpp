@@ -35,6 +35,12 @@
 //   --check-every=E         sweeps between two residual checks (default: tsteps)
 //   --lag=L                 the host decides on a check L checks behind the device (default 1,
 //                           0..8): with L >= 1 the device never idles for a check
+//   --source=poly|random[:AMP]   Poisson source term of the sweep, un = J(u) + s
+//                           (JacobiConfig::source): poly = the s for which the initial field
+//                           x^3 + y^2 is the discrete fixed point, random = uniform in
+//                           [-AMP, AMP) (default 1).  With --tblock the fused passes stay
+//                           Laplace passes and a block of B sweeps ends with one add
+//   --src-every=B           sweeps per source block (default tsteps; a multiple of it)
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -52,11 +58,32 @@
 
 using namespace gmt;
 
-// Serial host reference of the same problem (init, boundary, update order).
-static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool periodic, int axes = 3) {
+// gmt_fill_poly mode 5's hash of a lattice point (csrc/kernels/reduce.hip lattice_uniform)
+static double lattice_uniform(int64_t gx, int64_t gy, uint64_t seed) {
+  uint64_t k = (static_cast<uint64_t>(gy + (int64_t(1) << 30)) << 32) ^ static_cast<uint64_t>(gx + (int64_t(1) << 30));
+  k ^= seed;
+  k += 0x9E3779B97F4A7C15ull;
+  k = (k ^ (k >> 30)) * 0xBF58476D1CE4E5B9ull;
+  k = (k ^ (k >> 27)) * 0x94D049BB133111EBull;
+  k ^= k >> 31;
+  return static_cast<double>(k >> 11) * 0x1.0p-53;
+}
+
+// Serial host reference of the same problem (init, boundary, update order,
+// source: JacobiConfig::source 1 or 2 with `amp` and the engine's seed + 1).
+static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool periodic, int axes = 3,
+                                         int source = 0, double amp = 1.0, uint64_t seed = 0) {
   const int64_t ld = nx + 2;
   const double h = 1.0 / (static_cast<double>(ny > nx ? ny : nx) + 1);
-  std::vector<double> u((ny + 2) * ld), un;
+  std::vector<double> u((ny + 2) * ld), un, src;
+  if (source != 0) {
+    src.resize(ny * nx);
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) {
+        const double x = static_cast<double>(i) * h;
+        src[j * nx + i] = source == 1 ? -(1.5 * x + 0.5) * h * h : amp * (2.0 * lattice_uniform(i, j, seed + 1) - 1.0);
+      }
+  }
   for (int64_t j = 0; j < ny + 2; ++j)
     for (int64_t i = 0; i < nx + 2; ++i) {
       const double x = (i - 1) * h, y = (j - 1) * h;
@@ -78,6 +105,7 @@ static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool
       for (int64_t i = 1; i <= nx; ++i) {
         const double* p = &u[j * ld + i];
         un[j * ld + i] = 0.25 * ((p[-1] + p[1]) + (p[-ld] + p[ld]));
+        if (source != 0) un[j * ld + i] += src[(j - 1) * nx + i - 1];
       }
     std::swap(u, un);
   }
@@ -134,6 +162,24 @@ int main(int argc, char** argv) {
     std::fflush(stdout);
     MPI_Abort(MPI_COMM_WORLD, 1);
   }
+  // --source=poly | random[:AMP], --src-every=B
+  const std::string src_arg = cli.get("source", "");
+  if (!src_arg.empty()) {
+    const std::string kind = src_arg.substr(0, src_arg.find(':'));
+    c.source = kind == "poly" ? 1 : (kind == "random" ? 2 : -1);
+    if (c.source == 2 && src_arg.find(':') != std::string::npos)
+      c.source_amp = std::atof(src_arg.c_str() + src_arg.find(':') + 1);
+    c.src_every = static_cast<int>(cli.geti("src-every", 0));
+    const int ks = c.tblock ? (c.tsteps > 1 ? c.tsteps : 2) : 1;
+    if (c.source < 0 || !(c.source_amp >= 0) || !std::isfinite(c.source_amp) || c.src_every < 0 ||
+        (ks > 1 && c.src_every % ks != 0)) {
+      if (rank == 0)
+        std::printf("ERROR: --source=poly|random[:AMP] (AMP finite, >= 0) and --src-every a positive multiple of "
+                    "--tsteps (%d); got --source=%s --src-every=%d\n", ks, src_arg.c_str(), c.src_every);
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+  }
   // with one rank and no periodic wrap there is nothing to exchange; with a
   // periodic wrap a single rank exchanges with itself
   comm::Kind kind = comm::parse_kind(cli.get("transport", "auto"));
@@ -168,8 +214,14 @@ int main(int argc, char** argv) {
   size_t hbytes = 0, hmsgs = 0;
   int64_t lnx = 0, lny = 0;
   int sh_strips = 0;
+  int src_every = 0, src_setup_sweeps = 0;
+  double src_setup_ms = 0, src_mib = 0, src_err = -1;
   {
     JacobiSolver solver(*tr, c);
+    src_every = solver.src_every();
+    src_setup_sweeps = solver.source_setup_sweeps();
+    src_setup_ms = solver.source_setup_ms();
+    src_mib = static_cast<double>(solver.source_bytes()) / (1 << 20);
     graph = solver.graph_active();
     graph_sweep = solver.sweep_graph_active();
     graph_fused = solver.fused_graph_active();
@@ -224,7 +276,14 @@ int main(int argc, char** argv) {
       MPI_Gatherv(loc.data(), static_cast<int>(loc.size()), MPI_DOUBLE, g.data(), counts.data(),
                   displs.data(), MPI_DOUBLE, 0, MPI_COMM_WORLD);
       if (rank == 0) {
-        std::vector<double> ref = serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes);
+        std::vector<double> ref = serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes,
+                                                c.source, c.source_amp, c.seed);
+        // the poly source makes the initial field the discrete fixed point (fixed ring)
+        std::vector<double> u0;
+        if (c.source == 1 && c.init == 0 && !c.periodic) {
+          u0 = serial_jacobi(c.ny_global, c.nx_global, 0, c.periodic, c.periodic_axes);
+          src_err = 0;
+        }
         max_diff = 0;
         for (int r = 0; r < world; ++r) {
           const long long oy = all[4 * r], ox = all[4 * r + 1], ny = all[4 * r + 2], nx = all[4 * r + 3];
@@ -233,6 +292,10 @@ int main(int argc, char** argv) {
             for (long long i = 0; i < nx; ++i)
               max_diff = std::fmax(max_diff, std::fabs(blk[j * nx + i] -
                                                        ref[(oy + j) * c.nx_global + ox + i]));
+          if (!u0.empty())
+            for (long long j = 0; j < ny; ++j)
+              for (long long i = 0; i < nx; ++i)
+                src_err = std::fmax(src_err, std::fabs(blk[j * nx + i] - u0[(oy + j) * c.nx_global + ox + i]));
         }
       }
     }
@@ -268,6 +331,16 @@ int main(int argc, char** argv) {
     if (c.tb_shared != 0)
       std::printf("shared    = %d (rank 0: %d strips per shared hand-off group, 0 = per-strip launch)\n", c.tb_shared,
                   sh_strips);
+    if (c.source != 0) {
+      char amp[48] = "";
+      if (c.source == 2) std::snprintf(amp, sizeof(amp), ":%g", c.source_amp);
+      if (src_every > 0)
+        std::printf("source    = %s%s every %d sweeps (set-up %d sweeps, %0.3f ms, %0.1f MiB)\n",
+                    c.source == 1 ? "poly" : "random", amp, src_every, src_setup_sweeps, src_setup_ms, src_mib);
+      else
+        std::printf("source    = %s%s every 1 sweeps (set-up 0 sweeps, %0.3f ms, %0.1f MiB)\n",
+                    c.source == 1 ? "poly" : "random", amp, src_setup_ms, src_mib);
+    }
     if (solve_mode) {
       std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d sweeps, lag %d\n", so.tol, so.rtol,
                   so.norm ? "max" : "l2", so.check_every, so.lag);
@@ -291,6 +364,7 @@ int main(int argc, char** argv) {
     std::printf("residual  : %.10e\n", resid);
     if (max_diff >= 0)
       std::printf("check     : max|diff| vs serial = %.3e %s\n", max_diff, max_diff < 1e-10 ? "OK" : "FAIL");
+    if (src_err >= 0) std::printf("source err: max|u - u0| = %.3e\n", src_err);
     JsonRecord j;
     j.add("app", "mpi_jacobi2d").add("ranks", world).add("py", c.py).add("px", c.px)
         .add("ny", (long long)c.ny_global).add("nx", (long long)c.nx_global).add("transport", tr->name())
@@ -300,6 +374,9 @@ int main(int argc, char** argv) {
     if (solve_mode)
       j.add("converged", sr.converged != 0).add("sweeps", sr.sweeps).add("residual_sweeps", sr.residual_sweeps)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
+    if (c.source != 0)
+      j.add("source", c.source == 1 ? "poly" : "random").add("src_every", src_every > 0 ? src_every : 1)
+          .add("source_setup_ms", src_setup_ms);
     j.append_to(cli.get("json", ""));
   }
   tr.reset();

@@ -136,7 +136,9 @@ void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank,
   if (o.tsteps < 0 || o.tsteps > GMT_TB_MAX_SWEEPS || o.overlap < 0 || o.overlap > 2 || o.wg_waves < 0 ||
       o.wg_waves > 8 || o.seg_rows < 0 || o.exact < -1 || o.exact > 1 || o.init < 0 || o.init > 1 ||
       o.calibrate < 0 || o.calibrate > 1 || o.seed < 0 || o.seed >= (int64_t(1) << 53) || o.push < 0 || o.push > 1 ||
-      !(o.shared == -1 || o.shared == 0 || o.shared == 1 || o.shared == 2 || o.shared == 4))
+      !(o.shared == -1 || o.shared == 0 || o.shared == 1 || o.shared == 2 || o.shared == 4) || o.source < 0 ||
+      o.source > 3 || o.src_every < 0 || !(o.source_amp >= 0.0) || o.source_amp > 1e300 ||
+      (o.source != 0 && o.tsteps > 1 && o.src_every % o.tsteps != 0))
     return nullptr;
   auto* h = new Handle();
   h->t = gmt::engine_transport(rank, world, transport, ccl_id);
@@ -164,6 +166,9 @@ void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank,
   c.calibrate = o.calibrate != 0;
   c.push = o.push != 0;
   c.tb_shared = o.shared;
+  c.source = o.source;
+  c.src_every = o.src_every;
+  c.source_amp = o.source_amp;
   h->py = py;
   h->px = px;
   h->s = std::make_unique<gmt::JacobiSolver>(*h->t, c);
@@ -262,6 +267,16 @@ int gmt_engine_jacobi_copy_interior(void* p, double* host) {
   static_cast<Handle*>(p)->s->copy_interior(host);
   return 0;
 }
+int gmt_engine_jacobi_set_source(void* p, const double* host) {
+  if (!p) return 1;
+  gmt::watchdog_kick("engine: jacobi source set-up");
+  return static_cast<Handle*>(p)->s->set_source(host);
+}
+int gmt_engine_jacobi_source_plan(void* p, int steps, int out[3]) {
+  if (!p || !out) return 1;
+  static_cast<Handle*>(p)->s->source_plan(steps, out);
+  return 0;
+}
 int gmt_engine_plan_from_costs(int k, int ks, const double* cost, int measured, int* out, int max) {
   if (k < 0 || ks < 1 || ks > GMT_TB_MAX_SWEEPS || !cost) return -1;
   const std::vector<int> plan = gmt::plan_pass_sequence(k, ks, std::vector<double>(cost, cost + ks + 1), measured != 0);
@@ -290,6 +305,10 @@ double gmt_engine_jacobi_stat(void* p, int what) {
     case 0: return s.max_abs_u0();
     case 1: return s.measured_pass_ms(s.tsteps());
     case 2: return s.table_pass_ms(s.tsteps());
+    case 3: return s.max_abs_source();
+    case 4: return s.source_setup_ms();
+    case 5: return static_cast<double>(s.source_setup_sweeps());
+    case 6: return static_cast<double>(s.source_bytes());
     default: return 0.0;
   }
 }

@@ -19,7 +19,10 @@
 namespace gmt {
 
 namespace {
-constexpr double kC0 = 0.25;  // un = 1/4 (W + E + S + N): Laplace, no source term
+// un = 1/4 ((W + E) + (S + N)) [+ s]: the source engines (JacobiConfig::source)
+// store s itself and pass it as the kernels' f with c1 = 1 — o + 1.0 * s
+// rounds the same with or without fma contraction; Laplace engines pass no f
+constexpr double kC0 = 0.25;
 
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 }  // namespace
@@ -88,6 +91,12 @@ JacobiSolver::JacobiSolver(comm::Transport& t, const JacobiConfig& c) : t_(t), c
     std::printf("JacobiSolver: init must be 0 (analytic) or 1 (random), got %d\n", c.init);
     abort_job(EXIT_FAILURE);
   }
+  if (c.source < 0 || c.source > 3 || c.src_every < 0 || !(c.source_amp >= 0.0) || !std::isfinite(c.source_amp) ||
+      (c.source != 0 && ks_ > 1 && c.src_every % ks_ != 0)) {
+    std::printf("JacobiSolver: source must be 0..3, source_amp finite and >= 0, src_every 0 or a positive "
+                "multiple of tsteps (%d); got %d, %g, %d\n", ks_, c.source, c.source_amp, c.src_every);
+    abort_job(EXIT_FAILURE);
+  }
   g_ = ks_;
   yo_ = g_;
   xo_ = round_up(g_, 8);  // ghost columns fit left of the interior; 64-B aligned interior
@@ -114,10 +123,23 @@ JacobiSolver::JacobiSolver(comm::Transport& t, const JacobiConfig& c) : t_(t), c
   watchdog_kick("jacobi: max|u| all-reduce");
   umax_ = measure_max_abs();
   exact_ = c.exact == 1 || !(umax_ * std::ldexp(1.0, 2 * ks_) < 1e300);
+  if (c.source != 0) {
+    // the source and block fields, before capture_graphs: captured launches
+    // hold these pointers.  A source breaks "the initial field bounds every
+    // later one": a field grows by at most max|s| a sweep, and an int counts
+    // fewer than 2^31 sweeps
+    f_ = Buffer<double>(elems, GMT_SPACE_DEVICE);
+    gsrc_ = Buffer<double>(elems, GMT_SPACE_DEVICE);
+    fill_source();
+    smax_ = measure_max_source();
+    if (!source_bound_ok(smax_, ks_)) exact_ = true;
+  }
   // exact passes stop at the largest K whose kernel fits the register file
   // (the ghost ring keeps its width: wider than a pass needs is harmless)
   if (ks_ > 1 && exact_)
     while (ks_ > gmt_jacobi5tb_max_sweeps(1) || !gmt_jacobi5tb_supported(ks_)) --ks_;
+  // sweeps per source block (any count is correct: its passes are plan_passes')
+  if (c.source != 0 && ks_ > 1) src_every_ = c.src_every > 0 ? c.src_every : ks_;
   resid_ws_ = Buffer<double>(gmt_jacobi_resid_workspace(nx_, ny_) + 1, GMT_SPACE_DEVICE);
   {
     const char* ce = std::getenv("GMT_CLOCK");
@@ -137,6 +159,7 @@ JacobiSolver::JacobiSolver(comm::Transport& t, const JacobiConfig& c) : t_(t), c
   if (!push_on_ && ks_ > 1 && halo_[0]->active() && (c.overlap || c.overlap_auto)) split_cus();
   watchdog_kick("jacobi: halo plans ready");
   if (c.overlap_auto && !push_on_) autotune_overlap();
+  if (c.source != 0) build_block_field();
   if (c.graph) capture_graphs();
   watchdog_kick("jacobi: ready");
 }
@@ -198,7 +221,102 @@ void JacobiSolver::init_field() {
   GMT_CHECK("init sync", gmt_rt_stream_synchronize(s_));
   parity_ = 0;
   passes_ = 0;
+  advanced_ = false;
   fresh_[0] = fresh_[1] = false;  // periodic / neighbour ghosts come from an exchange
+}
+
+// ---- source term (cfg_.source) ----
+
+void JacobiSolver::fill_source() {
+  const JacobiConfig& c = cfg_;
+  const double h = 1.0 / (static_cast<double>(c.ny_global > c.nx_global ? c.ny_global : c.nx_global) + 1);
+  double* fi = f_.data() + xo_ + yo_ * ld_;
+  GMT_CHECK("memset", gmt_rt_memset_async(f_.data(), 0, f_.bytes(), s_));
+  // interior cell (i, j) is the global lattice point (ox_ + i, oy_ + j), as in init_field
+  if (c.source == 1)
+    GMT_CHECK("source fill", gmt_fill_poly(7, nx_, ny_, static_cast<double>(ox_), h, static_cast<double>(oy_), h, fi,
+                                           ld_, s_));
+  else if (c.source == 2)
+    GMT_CHECK("source fill", gmt_fill_poly(6, nx_, ny_, static_cast<double>(ox_), static_cast<double>(c.seed + 1),
+                                           static_cast<double>(oy_), c.source_amp, fi, ld_, s_));
+  GMT_CHECK("source sync", gmt_rt_stream_synchronize(s_));
+}
+
+double JacobiSolver::measure_max_source() {
+  Buffer<double> ws(static_cast<size_t>(gmt_diff_sq_workspace(nx_, ny_)) + 1, GMT_SPACE_DEVICE);
+  GMT_CHECK("abs max", gmt_abs_max(nx_, ny_, f_.data() + xo_ + yo_ * ld_, ld_, ws.data(), ws.data() + 1, s_));
+  t_.allreduce_max(ws.data(), 1, s_);
+  double m = 0.0;
+  GMT_CHECK("abs max D2H", gmt_rt_memcpy_async(&m, ws.data(), sizeof(double), s_));
+  GMT_CHECK("abs max sync", gmt_rt_stream_synchronize(s_));
+  return m;
+}
+
+bool JacobiSolver::source_bound_ok(double smax, int k) const {
+  return (umax_ + std::ldexp(smax, 31)) * std::ldexp(1.0, 2 * k) < 1e300;
+}
+
+// g = src_every_ single source sweeps from a zero field with a zero ring,
+// through the engine's own step (halo exchanges included: a neighbour's or a
+// periodic ghost carries that side's g), then the initial field again.
+void JacobiSolver::build_block_field() {
+  const double t0 = wtime();
+  src_setup_sweeps_ = 0;
+  if (src_every_ > 0) {
+    watchdog_kick("jacobi: source block field");
+    if (smax_ == 0.0) {  // a zero source (kind 3 before set_source): a zero block field
+      GMT_CHECK("memset", gmt_rt_memset_async(gsrc_.data(), 0, gsrc_.bytes(), s_));
+    } else {
+      for (int b = 0; b < 2; ++b) GMT_CHECK("memset", gmt_rt_memset_async(buf_[b].data(), 0, buf_[b].bytes(), s_));
+      parity_ = 0;
+      fresh_[0] = fresh_[1] = false;
+      for (int i = 0; i < src_every_; ++i) {
+        enqueue_step(parity_);
+        parity_ ^= 1;
+      }
+      GMT_CHECK("block field", gmt_rt_memcpy_async(gsrc_.data(), buf_[parity_].data(), gsrc_.bytes(), s_));
+      src_setup_sweeps_ = src_every_;
+    }
+    synchronize();
+  }
+  init_field();
+  src_setup_ms_ = (wtime() - t0) * 1e3;
+}
+
+void JacobiSolver::add_block_field() {
+  const int64_t off = xo_ + yo_ * ld_;
+  GMT_CHECK("source add", gmt_add2d(nx_, ny_, gsrc_.data() + off, ld_, buf_[parity_].data() + off, ld_, s_));
+  fresh_[parity_] = false;  // the ghost ring was not added to
+}
+
+int JacobiSolver::set_source(const double* host) {
+  if (cfg_.source != 3 || !host) return 1;
+  if (advanced_) return 2;
+  double m = 0.0;
+  for (int64_t i = 0; i < nx_ * ny_; ++i) m = std::max(m, std::isnan(host[i]) ? HUGE_VAL : std::fabs(host[i]));
+  {  // max over ranks: one decision for every rank
+    Buffer<double> d(1, GMT_SPACE_DEVICE);
+    GMT_CHECK("source H2D", gmt_rt_memcpy(d.data(), &m, sizeof(double)));
+    t_.allreduce_max(d.data(), 1, s_);
+    GMT_CHECK("source D2H", gmt_rt_memcpy_async(&m, d.data(), sizeof(double), s_));
+    GMT_CHECK("source sync", gmt_rt_stream_synchronize(s_));
+  }
+  if (ks_ > 1 && !exact_ && !source_bound_ok(m, ks_)) return 3;
+  GMT_CHECK("source H2D", gmt_rt_memcpy2d_async(f_.data() + xo_ + yo_ * ld_, ld_ * sizeof(double), host,
+                                                nx_ * sizeof(double), nx_ * sizeof(double), ny_, s_));
+  GMT_CHECK("source sync", gmt_rt_stream_synchronize(s_));
+  smax_ = m;
+  build_block_field();
+  return 0;
+}
+
+void JacobiSolver::source_plan(int k, int out[3]) const {
+  out[0] = out[1] = out[2] = 0;
+  if (cfg_.source == 0) return;
+  out[1] = src_every_;
+  if (k <= 0) return;
+  out[0] = src_every_ > 0 ? k / src_every_ : 0;
+  out[2] = src_every_ > 0 ? k % src_every_ : k;
 }
 
 double JacobiSolver::measure_max_abs() {
@@ -334,7 +452,7 @@ JacobiSolver::~JacobiSolver() {
 void JacobiSolver::sweep_full(int parity, double* resid) {
   const double* u = buf_[parity].data();
   double* un = buf_[parity ^ 1].data();
-  GMT_CHECK("jacobi sweep", gmt_jacobi5(xo_, nx_, yo_, ny_, u, un, ld_, nullptr, 0, kC0, 0.0, resid, s_));
+  GMT_CHECK("jacobi sweep", gmt_jacobi5(xo_, nx_, yo_, ny_, u, un, ld_, src_f(), src_ld(), kC0, src_c1(), resid, s_));
 }
 
 void JacobiSolver::enqueue_step(int parity) {
@@ -355,8 +473,8 @@ void JacobiSolver::enqueue_step(int parity) {
   // core: every cell whose 5-point stencil stays inside the interior; it
   // starts at an even column so the sweep keeps its 16-B vector path
   GMT_CHECK("event", gmt_rt_event_record(ev_start_, s_));
-  GMT_CHECK("core sweep", gmt_jacobi5(xo_ + 2, nx_ - 4, yo_ + 1, ny_ - 2, u, un, ld_, nullptr, 0,
-                                      kC0, 0.0, nullptr, s_));
+  GMT_CHECK("core sweep", gmt_jacobi5(xo_ + 2, nx_ - 4, yo_ + 1, ny_ - 2, u, un, ld_, src_f(), src_ld(),
+                                      kC0, src_c1(), nullptr, s_));
   // halo on the high-priority stream, concurrent with the core sweep
   GMT_CHECK("wait", gmt_rt_stream_wait_event(cs_, ev_start_));
   h.start(cs_);
@@ -367,7 +485,7 @@ void JacobiSolver::enqueue_step(int parity) {
   const int64_t y0 = yo_, y1 = yo_ + 1;
   const int64_t rects[16] = {xo_, nx_, y0,            1,       xo_,           nx_, yo_ + ny_ - 1, 1,
                              xo_, 2,   y1,            ny_ - 2, xo_ + nx_ - 2, 2,   y1,            ny_ - 2};
-  GMT_CHECK("frame sweep", gmt_jacobi5_rects(4, rects, u, un, ld_, nullptr, 0, kC0, 0.0, s_));
+  GMT_CHECK("frame sweep", gmt_jacobi5_rects(4, rects, u, un, ld_, src_f(), src_ld(), kC0, src_c1(), s_));
 }
 
 int JacobiSolver::halo_mask() const {
@@ -777,6 +895,24 @@ std::vector<int> plan_pass_sequence(int k, int ks, std::vector<double> cost, boo
 
 void JacobiSolver::run(int k) {
   in_run_ = true;
+  if (k > 0) advanced_ = true;
+  if (src_every_ > 0) {
+    // a source engine with fused passes: blocks of src_every_ sweeps — the
+    // Laplace passes as they are (graphs and inline halo included), then
+    // the block field added — and single source sweeps for the rest
+    for (int b = 0; b < k / src_every_; ++b) {
+      run_laplace(src_every_);
+      add_block_field();
+    }
+    for (int i = 0; i < k % src_every_; ++i) step();
+  } else {
+    run_laplace(k);  // single sweeps carry their source themselves
+  }
+  in_run_ = false;
+  watchdog_kick("jacobi steps enqueued");
+}
+
+void JacobiSolver::run_laplace(int k) {
   for (int K : plan_passes(k)) {
     if (K == 1) {
       step();
@@ -787,15 +923,15 @@ void JacobiSolver::run(int k) {
       parity_ ^= 1;
     }
   }
-  in_run_ = false;
-  watchdog_kick("jacobi steps enqueued");
 }
 
 void JacobiSolver::prepare(int k) {
   if (cfg_.calibrate && !calibrated_) calibrate_costs();
   std::vector<int> kinds;
-  for (int K : plan_passes(k))
+  // a source engine's run(k): the passes of a block, the add, the single source sweep
+  for (int K : plan_passes(src_every_ > 0 ? src_every_ : k))
     if (std::find(kinds.begin(), kinds.end(), K) == kinds.end()) kinds.push_back(K);
+  if (src_every_ > 0 && std::find(kinds.begin(), kinds.end(), 1) == kinds.end()) kinds.push_back(1);
   for (int K : kinds) {
     if (K == 1) {
       enqueue_step(parity_);
@@ -804,6 +940,7 @@ void JacobiSolver::prepare(int k) {
     }
     parity_ ^= 1;
   }
+  if (src_every_ > 0) add_block_field();
   synchronize();
   init_field();
 }
@@ -867,6 +1004,7 @@ void JacobiSolver::step() {
     enqueue_step(parity_);
   fresh_[parity_ ^ 1] = false;
   parity_ ^= 1;
+  advanced_ = true;
 }
 
 void JacobiSolver::synchronize() {
@@ -912,6 +1050,7 @@ double JacobiSolver::residual() {
   GMT_CHECK("resid D2H", gmt_rt_memcpy_async(&r, resid_ws_.data(), sizeof(double), s_));
   GMT_CHECK("resid sync", gmt_rt_stream_synchronize(s_));
   parity_ ^= 1;
+  advanced_ = true;
   return std::sqrt(r);
 }
 
@@ -927,8 +1066,8 @@ void JacobiSolver::enqueue_residual() {
     for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
   }
   if (!fresh_[parity_]) exchange_now(parity_);
-  GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, nullptr, 0, kC0, 0.0,
-                                                 rn_dev_.data(), rn_ws_.data(), s_));
+  GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, src_f(), src_ld(), kC0,
+                                                 src_c1(), rn_dev_.data(), rn_ws_.data(), s_));
   t_.allreduce_sum(rn_dev_.data(), 1, s_);
   t_.allreduce_max(rn_dev_.data(), 2, s_);
 }

@@ -221,10 +221,33 @@ int gmt_add_scalar(int64_t nx, int64_t ny, double v, double* z, int64_t ld, void
   return 0;
 }
 
+// csrc/kernels/add2d.hip: the same argument checks and codes, no kernel to pick
+int gmt_add2d_path(int64_t, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+
+int gmt_add2d(int64_t nx, int64_t ny, const double* g, int64_t ldg, double* u, int64_t ld, void*) {
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (!g || !u || ldg < nx || ld < nx) return 1;
+  for (int64_t iy = 0; iy < ny; ++iy)
+    for (int64_t ix = 0; ix < nx; ++ix) u[iy * ld + ix] += g[iy * ldg + ix];
+  return 0;
+}
+
 int gmt_fill_poly(int mode, int64_t nx, int64_t ny, double x0, double dx, double y0, double dy,
                   double* z, int64_t ld, void*) {
   for (int64_t j = 0; j < ny; ++j)
     for (int64_t i = 0; i < nx; ++i) {
+      if (mode == 6) {  // uniform [-dy, dy) on mode 5's hash (reduce.hip)
+        const double r = lattice_uniform(static_cast<int64_t>(x0) + i, static_cast<int64_t>(y0) + j,
+                                         static_cast<uint64_t>(dx));
+        z[j * ld + i] = dy * (2.0 * r - 1.0);
+        continue;
+      }
+      if (mode == 7) {  // the Jacobi source of mode 4's x^3 + y^2 (kernels.h)
+        const double xl = (x0 + static_cast<double>(i)) * dx;
+        z[j * ld + i] = -(1.5 * xl + 0.5) * dx * dx;
+        continue;
+      }
       if (mode == 5) {
         z[j * ld + i] = lattice_uniform(static_cast<int64_t>(x0) + i, static_cast<int64_t>(y0) + j,
                                         static_cast<uint64_t>(dx));

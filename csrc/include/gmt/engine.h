@@ -47,6 +47,12 @@ typedef struct gmt_engine_opts {
   int push;     /* 1: inline halo exchange of the fused passes (JacobiConfig::push) */
   int shared;   /* gmt_tb_opts.shared of the fused passes, inline-halo ones included
                    (JacobiConfig::tb_shared): -1, 0 (default), 1, 2 or 4 */
+  int source;   /* Poisson source term of the sweep (JacobiConfig::source): 0 none, 1 poly,
+                   2 uniform random in [-source_amp, source_amp), 3 supplied by the host
+                   (gmt_engine_jacobi_set_source) */
+  int src_every; /* sweeps per source block with tsteps > 1: 0 = tsteps, else a positive
+                    multiple of tsteps */
+  double source_amp; /* amplitude of source 2 (finite, >= 0) */
 } gmt_engine_opts;
 /* id: 128 bytes (RCCL unique id / control id) or NULL (local); NULL on invalid options */
 void* gmt_engine_jacobi_create(int64_t ny, int64_t nx, int py, int px, int rank, int world,
@@ -98,9 +104,23 @@ int gmt_engine_jacobi_tb_shared(void* h, int K);
  * initial field (first-launch costs stay out of a timed run). */
 int gmt_engine_jacobi_prepare(void* h, int steps);
 int gmt_engine_jacobi_copy_interior(void* h, double* host);
+/* Source 3: this rank's share of the sweep source, row-major [ny][nx] (the
+ * reverse of copy_interior); recomputes the block field and restores the
+ * initial field (JacobiSolver::set_source).  Only before the first sweep;
+ * collective.  0, or 1 not a source-3 engine / NULL, 2 a sweep has run, 3 the
+ * source is too large for the scaled levels (create with exact = 1). */
+int gmt_engine_jacobi_set_source(void* h, const double* host);
+/* What run(steps) enqueues on a source engine: out = {blocks, sweeps per block,
+ * single source sweeps after them} (JacobiSolver::source_plan; all zero
+ * without a source).  gmt_engine_jacobi_plan keeps describing Laplace passes:
+ * a block's are those of plan(out[1]). */
+int gmt_engine_jacobi_source_plan(void* h, int steps, int out[3]);
 /* what: 0 = max |u| of the initial field (all ranks; drives the exactness
  * guard), 1 = measured ms of a full tsteps pass (0 before a calibrated
- * prepare), 2 = the built-in cost table's ms for that pass on this share */
+ * prepare), 2 = the built-in cost table's ms for that pass on this share,
+ * 3 = max |s| of the source over all ranks, 4 / 5 = wall-clock ms / sweeps of
+ * the last set-up of the source block field, 6 = device bytes of the source
+ * and block fields */
 /* bitwise comparison of the current interiors of two engines of the same
  * problem and process grid (collective): out[0] = max |diff| over ranks,
  * out[1] = elements whose bits differ, summed over ranks */

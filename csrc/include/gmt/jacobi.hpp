@@ -96,6 +96,26 @@ struct JacobiConfig {
   // Each rank decides its own launch: a share narrower than a group keeps
   // the per-strip kernel.
   int tb_shared = 0;
+  // Poisson source term: a sweep is un = 1/4 ((W + E) + (S + N)) + s with a
+  // fixed field s (for -Laplace(u) = f on a mesh of width h: s = h^2/4 f).
+  // source: 0 none (Laplace: exactly the code paths of an engine without this
+  // option), 1 poly (gmt_fill_poly mode 7: the s for which init 0's
+  // x^3 + y^2 is the discrete fixed point), 2 uniform random in
+  // [-source_amp, source_amp) (mode 6, seed `seed + 1`), 3 supplied by the
+  // host (set_source; zero until then).
+  // With tblock the fused Laplace passes stay as they are, by superposition:
+  // a sweep is affine in (u, ring, s), so for a block of n sweeps
+  //   u(t+n) = L^n(u(t)) + g_n,
+  // L^n = n Laplace sweeps with the real ring (the fused passes, bitwise),
+  // g_n = n source sweeps from a zero field with a zero ring, computed once
+  // at set-up.  run(k) is k / src_every blocks — the passes of
+  // plan_passes(src_every), then one streaming add of g (gmt_add2d, 24 B per
+  // point) — and k % src_every single source sweeps.  src_every: sweeps per
+  // block, 0 = tsteps, a positive multiple of tsteps; ignored without tblock
+  // (every sweep is then a single source sweep).
+  int source = 0;
+  double source_amp = 1.0;
+  int src_every = 0;
 };
 
 // JacobiSolver::solve: sweep until the residual d = J(u) - u of the current
@@ -127,7 +147,9 @@ class JacobiSolver {
   JacobiSolver& operator=(const JacobiSolver&) = delete;
 
   void step();  // one sweep, asynchronous (compute stream)
-  void run(int k);  // k sweeps through the fused kernel (plan_passes) when tblock
+  // k sweeps through the fused kernel (plan_passes) when tblock; with a source
+  // and tblock: blocks of src_every sweeps (source_plan)
+  void run(int k);
   // cheapest sequence of fused passes (sweeps per pass <= tsteps) covering k sweeps
   std::vector<int> plan_passes(int k) const;
   void synchronize();
@@ -152,6 +174,26 @@ class JacobiSolver {
   // field: first-launch costs (code object, occupancy query) stay out of a
   // timed run(k)
   void prepare(int k);
+  // Source kind 3: this rank's share of s, row-major [ny][nx] (host memory,
+  // the reverse of copy_interior).  Recomputes the block field and restores
+  // the initial field.  Only before the first sweep (or after a prepare());
+  // collective.  0, or non-zero with nothing changed: 1 not a kind-3 engine or
+  // a NULL pointer, 2 a sweep has run, 3 the source is too large for the
+  // scaled levels of the fused passes (construct with exact = 1).
+  int set_source(const double* host_interior);
+  // What run(k) enqueues on a source engine: {blocks, sweeps per block, single
+  // source sweeps after them}; {0, 0, k} with a source and no tblock, all zero
+  // without a source.  plan_passes keeps describing Laplace passes: those of
+  // one block are plan_passes(src_every).
+  void source_plan(int k, int out[3]) const;
+  int source() const { return cfg_.source; }
+  int src_every() const { return src_every_; }
+  double max_abs_source() const { return smax_; }
+  // sweeps and wall-clock ms of the last set-up of the block field; its and
+  // the source field's device bytes
+  int source_setup_sweeps() const { return src_setup_sweeps_; }
+  double source_setup_ms() const { return src_setup_ms_; }
+  size_t source_bytes() const { return f_.bytes() + gsrc_.bytes(); }
   bool exact() const { return exact_; }
   // local interior, row-major [ny][nx] (host memory)
   void copy_interior(double* host) const;
@@ -230,6 +272,16 @@ class JacobiSolver {
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
   void push_pass(int parity, int k);   // the pass launch alone
   void push_handover();                // the hand-over launch alone (push_mask_ != 0)
+  void run_laplace(int k);             // k sweeps of the Laplace operator through plan_passes(k)
+  void fill_source();                  // f_ of kinds 1 and 2, zero for kind 3
+  double measure_max_source();         // max |s| over every rank (gmt_abs_max)
+  bool source_bound_ok(double smax, int k) const;  // (max|u0| + 2^31 smax) * 4^k stays finite
+  // the kernels' f, ldf, c1: the source field with c1 = 1, or none
+  const double* src_f() const { return f_.data(); }
+  int64_t src_ld() const { return f_.data() ? ld_ : 0; }
+  double src_c1() const { return f_.data() ? 1.0 : 0.0; }
+  void build_block_field();            // gsrc_ = src_every_ source sweeps from zero, then init_field()
+  void add_block_field();              // current interior += gsrc_ (gmt_add2d on s_)
 
   comm::Transport& t_;
   JacobiConfig cfg_;
@@ -240,6 +292,15 @@ class JacobiSolver {
   bool exact_ = false;                         // gmt_tb_opts.exact for the fused passes
   Neighbors nb_;
   Buffer<double> buf_[2];
+  // source engines (cfg_.source != 0), both in buf_'s layout: the sweep
+  // source s (the kernels' f with c1 = 1) and the block field g of src_every_
+  // sweeps; allocated before capture_graphs, never reallocated
+  Buffer<double> f_, gsrc_;
+  int src_every_ = 0;     // sweeps per block; 0: no blocks (no source, or no tblock)
+  double smax_ = 0.0;     // max |s| over every rank
+  bool advanced_ = false;  // a sweep has run since the field was (re)initialised
+  int src_setup_sweeps_ = 0;
+  double src_setup_ms_ = 0.0;
   std::unique_ptr<Halo2D> halo_[2];
   Buffer<double> resid_ws_;
   // residual_norm / solve: the kernel's workspace, its device result and the

@@ -155,7 +155,13 @@ int gmt_diff_bits(int64_t nx, int64_t ny, const double* a, int64_t lda, const do
  *      indices, no fma contraction (bitwise reproducible on the host),
  *      5: uniform [0, 1) random field, a counter-based hash (splitmix64) of
  *      the integer lattice point (x0 + i, y0 + j) with seed (uint64) dx —
- *      decomposition-independent random init. */
+ *      decomposition-independent random init.
+ *      Jacobi source terms (JacobiConfig::source), both on the integer lattice:
+ *      6: uniform [-dy, dy): dy * (2 r - 1) with r mode 5's hash of the same
+ *      point and seed dx (no contraction: 2 r - 1 is exact, one rounding),
+ *      7: -(1.5*x + 0.5)*dx*dx with x = (x0 + i)*dx, no contraction — the
+ *      sweep source s = -h^2/4 (6x + 2) for which mode 4's x^3 + y^2
+ *      (dx = dy = h) is the discrete fixed point of un = J(u) + s. */
 int gmt_fill_poly(int mode, int64_t nx, int64_t ny, double x0, double dx, double y0,
                   double dy, double* z, int64_t ld, void* stream);
 /* Per-exchange halo check (the apps' --check): counts the cells of the
@@ -168,6 +174,18 @@ int gmt_fill_poly(int mode, int64_t nx, int64_t ny, double x0, double dx, double
 int gmt_poly_check(int64_t nx, int64_t ny, double x0, double dx, double y0, double dy, double offset,
                    double rtol, const double* z, int64_t ld, unsigned* bad, void* stream);
 int gmt_add_scalar(int64_t nx, int64_t ny, double v, double* z, int64_t ld, void* stream);
+
+/* ---- u[y][x] += g[y][x] over nx x ny (pitches ld / ldg doubles), one
+ *      rounding per cell; cells outside the region are untouched
+ *      (csrc/kernels/add2d.hip).  The streaming add that ends a Poisson block
+ *      of the Jacobi engine: u(t+n) = L^n(u(t)) + g_n (gmt/jacobi.hpp
+ *      JacobiConfig::source).  24 B per point.  nx == 0 or ny == 0 launches
+ *      nothing and returns 0; a negative extent, a NULL pointer or a pitch
+ *      shorter than nx is refused (non-zero, the same on both backends). */
+int gmt_add2d(int64_t nx, int64_t ny, const double* g, int64_t ldg, double* u, int64_t ld, void* stream);
+/* GMT_PATH_PT (column pairs: both pointers 16-B aligned, both pitches even; an
+ * odd nx keeps it with a scalar last column) or GMT_PATH_SCALAR */
+int gmt_add2d_path(int64_t nx, const double* g, int64_t ldg, const double* u, int64_t ld);
 
 /* ---- 2-D 5-point Jacobi sweep (the BASELINE "5-pt Jacobi" extension):
  *      for y in [y0, y0+ny), x in [x0, x0+nx) (absolute array coordinates):

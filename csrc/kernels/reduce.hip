@@ -273,6 +273,19 @@ __global__ __launch_bounds__(kBlock) void fill_poly_kernel(int mode, int64_t nx,
                                       static_cast<uint64_t>(dx));
     return;
   }
+  if (mode == 6) {  // uniform [-dy, dy) on mode 5's lattice hash: 2 r - 1 is exact, one rounding
+#pragma clang fp contract(off)
+    const double r = lattice_uniform(static_cast<int64_t>(x0) + ix, static_cast<int64_t>(y0) + iy,
+                                     static_cast<uint64_t>(dx));
+    z[iy * ld + ix] = dy * (2.0 * r - 1.0);
+    return;
+  }
+  if (mode == 7) {  // the Jacobi source of x^3 + y^2 on mode 4's lattice (kernels.h)
+#pragma clang fp contract(off)
+    const double x = (x0 + static_cast<double>(ix)) * dx;
+    z[iy * ld + ix] = -(1.5 * x + 0.5) * dx * dx;
+    return;
+  }
   if (mode == 4) {
     // integer lattice: x = (x0 + ix) * dx with x0 an integer index (exact
     // sum, one rounding) and no fma contraction, so a NumPy reference
@@ -461,5 +474,5 @@ extern "C" int gmt_device_synchronize(void) { return static_cast<int>(hipDeviceS
 extern "C" const char* gmt_build_info(void) {
   return "libgmt gfx950 (CDNA4) kernels: daxpy, stencil5 1d/2d (dim 1: LDS-DMA pipeline), jacobi5, jacobi5_resid, "
          "jacobi5tb (1-20 fused sweeps, 4 columns per lane), ipc_exchange, signal_wait, "
-         "copy2d_batched, sum_axis, sum, diff_sq, diff_bits, abs_max, fill_poly; built " __DATE__ " " __TIME__;
+         "copy2d_batched, sum_axis, sum, diff_sq, diff_bits, abs_max, fill_poly, add2d; built " __DATE__ " " __TIME__;
 }

@@ -173,6 +173,8 @@ _SIGS = {
     "gmt_stage_scatter": (c_int, [c_int, c_vp, c_int, c_vp]),
     "gmt_poly_check": (c_int, [c_i64, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp]),
     "gmt_add_scalar": (c_int, [c_i64, c_i64, c_dbl, c_vp, c_i64, c_vp]),
+    "gmt_add2d": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_add2d_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
     "gmt_error_string": (ctypes.c_char_p, [c_int]),
     "gmt_device_synchronize": (c_int, []),
     "gmt_xcd_of_workgroups": (c_int, [c_int, c_vp, c_vp]),

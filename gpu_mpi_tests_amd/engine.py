@@ -39,6 +39,7 @@ HOST_ENGINE = os.path.join(_ROOT, "build", "lib-host", "libgmt_engine.so")
 
 LOCAL, RCCL, IPC = 0, 1, 2
 INITS = {"analytic": 0, "random": 1}  # JacobiConfig::init
+SOURCES = {None: 0, "poly": 1, "random": 2, "host": 3}  # JacobiConfig::source ("host": an ndarray)
 _KINDS = {"local": LOCAL, "rccl": RCCL, "ipc": IPC}
 MAX_TSTEPS = 20  # GMT_TB_MAX_SWEEPS (csrc/include/gmt/kernels.h)
 _libs: dict[str, ctypes.CDLL] = {}
@@ -48,7 +49,9 @@ class EngineOpts(ctypes.Structure):
     """gmt_engine_opts (csrc/include/gmt/engine.h)."""
     _fields_ = [(n, ctypes.c_int) for n in
                 ("periodic", "overlap", "graph", "tsteps", "wg_waves", "seg_rows", "exact", "init",
-                 "calibrate")] + [("seed", ctypes.c_int64), ("push", ctypes.c_int), ("shared", ctypes.c_int)]
+                 "calibrate")] + [("seed", ctypes.c_int64), ("push", ctypes.c_int), ("shared", ctypes.c_int),
+                                  ("source", ctypes.c_int), ("src_every", ctypes.c_int),
+                                  ("source_amp", ctypes.c_double)]
 
 
 class SolveOpts(ctypes.Structure):
@@ -129,6 +132,10 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_prepare.restype = c_int
     lib.gmt_engine_jacobi_copy_interior.argtypes = [vp, vp]
     lib.gmt_engine_jacobi_copy_interior.restype = c_int
+    lib.gmt_engine_jacobi_set_source.argtypes = [vp, vp]
+    lib.gmt_engine_jacobi_set_source.restype = c_int
+    lib.gmt_engine_jacobi_source_plan.argtypes = [vp, c_int, ctypes.POINTER(c_int)]
+    lib.gmt_engine_jacobi_source_plan.restype = c_int
     lib.gmt_engine_jacobi_compare.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
     lib.gmt_engine_jacobi_compare.restype = c_int
     lib.gmt_engine_jacobi_clock.argtypes = [vp, c_int, ctypes.POINTER(ctypes.c_double)]
@@ -314,8 +321,20 @@ class NativeJacobi:
                  overlap: "bool | str" = True, graph: bool = True,
                  tblock: bool | int = False, wg_waves: int = 0, seg_rows: int = 0, exact: int = -1,
                  transport: str = "auto", init: str = "analytic", seed: int = 0, calibrate: bool = False,
-                 push: bool = False, shared: int = 0):
-        """push: the fused passes exchange their halo inline (each pass stores
+                 push: bool = False, shared: int = 0, source: "str | np.ndarray | None" = None,
+                 source_amp: float = 1.0, src_every: int = 0):
+        """source: a Poisson source term, the sweep becomes
+        ``un = 0.25*((W+E)+(S+N)) + s`` (JacobiConfig::source): None (Laplace),
+        "poly" (the s for which the analytic initial field x^3 + y^2 is the
+        discrete fixed point), "random" (uniform in [-source_amp, source_amp),
+        a hash of the global lattice point and ``seed + 1``) or an ndarray,
+        this rank's ``[ny][nx]`` share of s.  With ``tblock`` the fused
+        Laplace passes stay as they are: ``run`` advances in blocks of
+        ``src_every`` sweeps (0 = tsteps, else a positive multiple of it), each
+        the passes of ``plan(src_every)`` and one streaming add of a block
+        field computed at set-up (gmt_add2d), then single source sweeps for the
+        rest (:meth:`source_plan`).
+        push: the fused passes exchange their halo inline (each pass stores
         its output faces straight into the neighbours' ghost cells over IPC
         mappings, then one hand-over launch; gmt/jacobi.hpp JacobiConfig::push).
         Needs the IPC transport when a neighbour is another rank; silently the
@@ -364,11 +383,24 @@ class NativeJacobi:
         if not 0 <= int(seed) < 1 << 53:
             raise ValueError("seed must be in [0, 2^53)")
         self.init, self.seed = init, int(seed)
+        src_arr = None
+        if isinstance(source, np.ndarray):
+            src_arr, source = source, "host"
+        if source not in SOURCES:
+            raise ValueError(f"source must be None, 'poly', 'random' or an ndarray, got {source!r}")
+        source_amp = float(source_amp)
+        if not np.isfinite(source_amp) or source_amp < 0:
+            raise ValueError(f"source_amp must be finite and >= 0, got {source_amp!r}")
+        if isinstance(src_every, bool) or int(src_every) < 0 or (source and ks > 1 and int(src_every) % ks):
+            raise ValueError(f"src_every must be 0 or a positive multiple of the {ks} sweeps per fused pass, "
+                             f"got {src_every!r}")
+        self.source = source
         opts = EngineOpts(periodic=int(bool(periodic)), overlap=2 if auto else int(bool(overlap)),
                           graph=int(bool(graph)), tsteps=ks, wg_waves=int(wg_waves),
                           seg_rows=int(seg_rows), exact=int(exact), init=INITS[init],
                           calibrate=int(bool(calibrate)), seed=int(seed), push=int(bool(push)),
-                          shared=int(shared))
+                          shared=int(shared), source=SOURCES[source], src_every=int(src_every),
+                          source_amp=source_amp)
         with _StdoutToStderr():
             self.h = self.lib.gmt_engine_jacobi_create(ny, nx, py, px, e.rank, e.world_size, transport,
                                                        cid, ctypes.byref(opts))
@@ -393,6 +425,9 @@ class NativeJacobi:
         self.graph_fused = bool(self.lib.gmt_engine_jacobi_graphs(self.h) & 2)
         self.overlap = bool(overlap_on)
         self.transport = transport_label(kind, e)
+        self.src_every = self.source_plan(0)["src_every"]
+        if src_arr is not None:
+            self.set_source(src_arr)
 
     # ------------------------------------------------------------------
     def run(self, steps: int) -> None:
@@ -406,6 +441,42 @@ class NativeJacobi:
         buf = (ctypes.c_int * max(1, steps))()
         n = self.lib.gmt_engine_jacobi_plan(self.h, int(steps), buf, max(1, steps))
         return list(buf[:n])
+
+    def source_plan(self, steps: int) -> dict:
+        """What ``run(steps)`` enqueues on a source engine: ``blocks`` of
+        ``src_every`` sweeps (the fused passes of ``plan(src_every)``, then the
+        add of the block field) and ``tail`` single source sweeps.  All zero
+        without a source; ``plan`` keeps describing Laplace passes."""
+        out = (ctypes.c_int * 3)()
+        if self.lib.gmt_engine_jacobi_source_plan(self.h, int(steps), out):
+            raise EngineError("gmt_engine_jacobi_source_plan failed")
+        return {"blocks": int(out[0]), "src_every": int(out[1]), "tail": int(out[2])}
+
+    def set_source(self, s: np.ndarray) -> None:
+        """This rank's ``[ny][nx]`` share of the sweep source of an engine made
+        with an ndarray ``source`` (JacobiSolver::set_source): the block field
+        is recomputed and the initial field restored.  Only before the first
+        sweep (or right after :meth:`prepare`).  An array of the global shape
+        is cut to this rank's share.  Collective."""
+        a = np.asarray(s, dtype=np.float64)
+        if a.shape == (self.ny_g, self.nx_g) and a.shape != (self.ny, self.nx):
+            a = a[self.off_y:self.off_y + self.ny, self.off_x:self.off_x + self.nx]
+        a = np.ascontiguousarray(a)
+        if a.shape != (self.ny, self.nx):
+            raise ValueError(f"set_source: this rank's share is {(self.ny, self.nx)}, got {a.shape}")
+        rc = self.lib.gmt_engine_jacobi_set_source(self.h, a.ctypes.data)
+        if rc:
+            raise EngineError({1: "set_source needs an engine made with an ndarray source",
+                               2: "set_source: a sweep has already run",
+                               3: "set_source: the source is too large for the scaled levels of the fused "
+                                  "passes (use exact=1)"}.get(rc, f"set_source failed: {rc}"))
+
+    def source_setup(self) -> dict:
+        """The last set-up of the block field: single source sweeps run, wall-clock
+        ms, device MiB of the source and block fields, max |s| over all ranks."""
+        st = self.lib.gmt_engine_jacobi_stat
+        return {"sweeps": int(st(self.h, 5)), "ms": float(st(self.h, 4)), "mib": float(st(self.h, 6)) / 2 ** 20,
+                "max_abs": float(st(self.h, 3))}
 
     def prepare(self, steps: int) -> None:
         """One pass of every pass type ``run(steps)`` uses, then the initial field again."""
@@ -638,14 +709,36 @@ def initial_field(ny: int, nx: int, init: str = "analytic", seed: int = 0) -> np
     return (x[None, :] * x[None, :] * x[None, :]) + (y[:, None] * y[:, None])
 
 
+def source_field(ny: int, nx: int, source: "str | np.ndarray | None", seed: int = 0,
+                 source_amp: float = 1.0) -> np.ndarray:
+    """The engine's sweep source s over the global interior, ny x nx, bitwise:
+    "poly" is gmt_fill_poly mode 7, "random" mode 6 with seed ``seed + 1``."""
+    if source is None:
+        return np.zeros((ny, nx))
+    if isinstance(source, np.ndarray):
+        return np.asarray(source, dtype=np.float64)
+    if source == "poly":
+        h = 1.0 / (max(ny, nx) + 1)
+        x = np.arange(nx, dtype=np.float64) * h
+        return np.broadcast_to((-(1.5 * x + 0.5) * h * h)[None, :], (ny, nx)).copy()
+    if source == "random":
+        gx = np.broadcast_to(np.arange(nx, dtype=np.int64)[None, :], (ny, nx))
+        gy = np.broadcast_to(np.arange(ny, dtype=np.int64)[:, None], (ny, nx))
+        return float(source_amp) * (2.0 * lattice_uniform(gx, gy, seed + 1) - 1.0)
+    raise ValueError(f"source must be None, 'poly', 'random' or an ndarray, got {source!r}")
+
+
 def serial_jacobi(ny: int, nx: int, steps: int, periodic: bool = False, init: str = "analytic",
-                  seed: int = 0) -> np.ndarray:
+                  seed: int = 0, source: "str | np.ndarray | None" = None, source_amp: float = 1.0) -> np.ndarray:
     """NumPy reference of exactly the engine's problem (init, boundary, update):
     bitwise — the engine fills x^3 + y^2 on the same integer lattice with the
     same operation order (gmt_fill_poly mode 4), or the same hashed random
-    field (mode 5), and sweeps in the same order."""
+    field (mode 5), and sweeps in the same order.  ``source``: the single
+    source sweeps ``un = 0.25*(...) + s`` (:func:`source_field`); the engine's
+    fused blocks agree with them to rounding, not bitwise."""
     u = initial_field(ny, nx, init, seed)
     un = u.copy()
+    s = None if source is None else source_field(ny, nx, source, seed, source_amp)
     for _ in range(steps):
         if periodic:
             u[1:-1, 0] = u[1:-1, -2]
@@ -653,5 +746,7 @@ def serial_jacobi(ny: int, nx: int, steps: int, periodic: bool = False, init: st
             u[0, 1:-1] = u[-2, 1:-1]
             u[-1, 1:-1] = u[1, 1:-1]
         un[1:-1, 1:-1] = 0.25 * ((u[1:-1, :-2] + u[1:-1, 2:]) + (u[:-2, 1:-1] + u[2:, 1:-1]))
+        if s is not None:
+            un[1:-1, 1:-1] += s
         u, un = un, u
     return u[1:-1, 1:-1].copy()

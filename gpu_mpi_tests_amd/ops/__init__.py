@@ -10,6 +10,8 @@ and ``jacobi5tb`` (K fused sweeps per memory pass).
 """
 from .kernels import (  # noqa: F401
     abs_max,
+    add2d,
+    add2d_path,
     copy2d_batched,
     daxpy,
     diff_norm,

@@ -61,6 +61,35 @@ def daxpy(a: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _add2d_views(g: torch.Tensor, u: torch.Tensor):
+    _check2d(g, "add2d.g")
+    _check2d(u, "add2d.u")
+    if tuple(g.shape) != tuple(u.shape):
+        raise ValueError(f"add2d: shape mismatch {tuple(g.shape)} vs {tuple(u.shape)}")
+    return u.shape[0], u.shape[1]
+
+
+def add2d(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """In-place ``u += g`` over a 2-D fp64 region (views into padded storage
+    welcome: each tensor's ``stride(0)`` is its row pitch), one rounding per
+    cell; nothing outside the region is touched (gmt_add2d).  The add that
+    ends a source block of the Jacobi engine."""
+    ny, nx = _add2d_views(g, u)
+    if not _is_dev(u):
+        u += g
+        return u
+    _native.check(_native.lib().gmt_add2d(nx, ny, g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0),
+                                          _stream(u)), "gmt_add2d")
+    return u
+
+
+def add2d_path(g: torch.Tensor, u: torch.Tensor) -> int:
+    """The kernel :func:`add2d` would launch for these device tensors
+    (gmt_add2d_path, no launch): PATH_PT (column pairs) or PATH_SCALAR."""
+    _, nx = _add2d_views(g, u)
+    return int(_native.lib().gmt_add2d_path(nx, g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0)))
+
+
 # ------------------------------------------------------------ 5-tap stencils
 def stencil5_1d(inp: torch.Tensor, out: torch.Tensor | None = None, scale: float = 1.0,
                 coef=DERIV5) -> torch.Tensor:
