@@ -15,6 +15,9 @@
 //      the sweep with residual (16 B/point) and gmt_sum, at 8192^2 and 32768^2
 //      --only=add2d [--reps=5]: the source-block add (gmt_add2d) alternated with
 //      gmt_daxpy on the same element count (24 B/point each)
+//      --only=cg [--reps=5] [--cg-n=N]: the three launches of a conjugate-gradient
+//      iteration (gmt_cg_apply 16 B/point, gmt_cg_update 48, gmt_cg_dir 24), each
+//      alternated with gmt_daxpy on the same element count
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -384,6 +387,61 @@ int main(int argc, char** argv) {
       }
       std::printf("add2d %lldx%lld  add2d / daxpy = %.4f  (best of %d)\n", (long long)n, (long long)n,
                   st[0].min() / st[1].min(), reps);
+    }
+  }
+  if (only.find("cg") != std::string::npos) {
+    // --only=cg: the kernels of JacobiSolver::cg in the engine's layout
+    // (interior at column 8, pitch padded to 64) at 8192^2, each against
+    // gmt_daxpy on n * n contiguous elements (24 B per element), --reps=5
+    // rounds in the order A B B A; the best of the rounds is compared.
+    // GB/s from the compulsory bytes: apply 16, update 48, dir 24 B per point.
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    const int64_t n = cli.geti("cg-n", 8192);
+    const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64;
+    const size_t elems = static_cast<size_t>(ld) * (n + 2);
+    Buffer<double> x(elems, GMT_SPACE_DEVICE), r(elems, GMT_SPACE_DEVICE), p(elems, GMT_SPACE_DEVICE),
+        q(elems, GMT_SPACE_DEVICE), sc(8, GMT_SPACE_DEVICE),
+        ws(static_cast<size_t>(gmt_cg_workspace(n, n)), GMT_SPACE_DEVICE);
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, x.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(3, ld, n + 2, 0.0, 1e-9, 0.0, 0.0, r.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, p.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(3, ld, n + 2, 0.0, 1e-9, 0.0, 0.0, q.data(), ld, s));
+    GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+    // coefficients a = 1e-3 (update) and b = 0.5 (dir): the fields stay bounded over the repeats
+    const double host_sc[8] = {1e-3, 1.0, 0.5, 1.0, 0, 0, 0, 0};
+    GMT_CHECK("scalars", gmt_rt_memcpy(sc.data(), host_sc, sizeof(host_sc)));
+    int64_t seg = 0;
+    const int apply_path = gmt_cg_apply_path(xo, n, n, p.data(), ld, nullptr, 0, q.data(), ld, &seg);
+    std::printf("cg %lldx%lld  apply path %d (%lld rows per segment), update path %d, dir path %d, pitch %lld\n",
+                (long long)n, (long long)n, apply_path, (long long)seg,
+                gmt_cg_update_path(xo, p.data(), ld, q.data(), ld, x.data(), ld, r.data(), ld),
+                gmt_cg_dir_path(xo, r.data(), ld, p.data(), ld), (long long)ld);
+    const std::function<void()> kernel[3] = {
+        [&] { GMT_CHECK("cg_apply", gmt_cg_apply(0, xo, n, 1, n, p.data(), ld, nullptr, 0, 0.25, 0.0, q.data(), ld,
+                                                 sc.data() + 4, ws.data(), s)); },
+        [&] { GMT_CHECK("cg_update", gmt_cg_update(xo, n, 1, n, sc.data(), sc.data() + 1, p.data(), ld, q.data(), ld,
+                                                   x.data(), ld, r.data(), ld, sc.data() + 6, ws.data(), s)); },
+        [&] { GMT_CHECK("cg_dir", gmt_cg_dir(xo, n, 1, n, sc.data() + 2, sc.data() + 3, r.data(), ld, p.data(), ld, s)); }};
+    const std::function<void()> daxpy = [&] { GMT_CHECK("daxpy", gmt_daxpy(n * n, 1e-3, q.data(), x.data(), s)); };
+    const char* name[3] = {"cg_apply", "cg_update", "cg_dir"};
+    const double bytes[3] = {16.0, 48.0, 24.0};
+    for (int k = 0; k < 3; ++k) {
+      Stats st[2];
+      const int order[4] = {0, 1, 1, 0};
+      for (int rep = 0; rep < reps; ++rep)
+        for (int o = 0; o < 4; ++o) {
+          const int v = order[o];
+          const double ms = time_ms(s, iters, v == 0 ? kernel[k] : daxpy);
+          st[v].add(ms);
+          std::printf("cg %lldx%lld rep %d  %-9s %9.4f ms\n", (long long)n, (long long)n, rep, v == 0 ? name[k] : "daxpy",
+                      ms);
+        }
+      char shape[64];
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+      report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
+      report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
+      std::printf("cg %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
+                  (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
     }
   }
   if (only.find("pack") != std::string::npos) {

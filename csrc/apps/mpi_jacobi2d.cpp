@@ -41,6 +41,16 @@
 //                           [-AMP, AMP) (default 1).  With --tblock the fused passes stay
 //                           Laplace passes and a block of B sweeps ends with one add
 //   --src-every=B           sweeps per source block (default tsteps; a multiple of it)
+//   --init=analytic|random  the initial field and Dirichlet ring (JacobiConfig::init): x^3 + y^2,
+//                           or uniform [0, 1) hashed from the lattice point and --seed=S (default 0)
+//   --cg                    conjugate gradients on (I - J) u = b instead of sweeps
+//                           (JacobiSolver::cg; Dirichlet only): --tol / --rtol / --norm / --lag as
+//                           above, --check-every=E iterations (default 10), n_iter the iteration
+//                           cap (rounded up to a multiple of E).  With neither --tol nor --rtol:
+//                           exactly n_iter iterations, and the time per iteration.  --check then
+//                           runs the same number of iterations of the serial whole-problem CG and
+//                           compares within 1e-10 * max|u0| (dot products depend on the
+//                           decomposition: not bitwise)
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -69,26 +79,37 @@ static double lattice_uniform(int64_t gx, int64_t gy, uint64_t seed) {
   return static_cast<double>(k >> 11) * 0x1.0p-53;
 }
 
-// Serial host reference of the same problem (init, boundary, update order,
-// source: JacobiConfig::source 1 or 2 with `amp` and the engine's seed + 1).
-static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool periodic, int axes = 3,
-                                         int source = 0, double amp = 1.0, uint64_t seed = 0) {
+// The engine's sweep source over the global interior (JacobiConfig::source 1
+// or 2 with `amp` and the engine's seed + 1), and its initial field with the
+// ghost ring (JacobiConfig::init), (ny + 2) x (nx + 2).
+static std::vector<double> serial_source(int64_t ny, int64_t nx, int source, double amp, uint64_t seed) {
+  const double h = 1.0 / (static_cast<double>(ny > nx ? ny : nx) + 1);
+  std::vector<double> src(ny * nx);
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) {
+      const double x = static_cast<double>(i) * h;
+      src[j * nx + i] = source == 1 ? -(1.5 * x + 0.5) * h * h : amp * (2.0 * lattice_uniform(i, j, seed + 1) - 1.0);
+    }
+  return src;
+}
+static std::vector<double> serial_init(int64_t ny, int64_t nx, int init, uint64_t seed) {
   const int64_t ld = nx + 2;
   const double h = 1.0 / (static_cast<double>(ny > nx ? ny : nx) + 1);
-  std::vector<double> u((ny + 2) * ld), un, src;
-  if (source != 0) {
-    src.resize(ny * nx);
-    for (int64_t j = 0; j < ny; ++j)
-      for (int64_t i = 0; i < nx; ++i) {
-        const double x = static_cast<double>(i) * h;
-        src[j * nx + i] = source == 1 ? -(1.5 * x + 0.5) * h * h : amp * (2.0 * lattice_uniform(i, j, seed + 1) - 1.0);
-      }
-  }
+  std::vector<double> u((ny + 2) * ld);
   for (int64_t j = 0; j < ny + 2; ++j)
     for (int64_t i = 0; i < nx + 2; ++i) {
       const double x = (i - 1) * h, y = (j - 1) * h;
-      u[j * ld + i] = x * x * x + y * y;
+      u[j * ld + i] = init == 1 ? lattice_uniform(i - 1, j - 1, seed) : x * x * x + y * y;
     }
+  return u;
+}
+
+// Serial host reference of the same problem (init, boundary, update order, source).
+static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool periodic, int axes = 3,
+                                         int source = 0, double amp = 1.0, uint64_t seed = 0, int init = 0) {
+  const int64_t ld = nx + 2;
+  std::vector<double> u = serial_init(ny, nx, init, seed), un, src;
+  if (source != 0) src = serial_source(ny, nx, source, amp, seed);
   un = u;
   for (int s = 0; s < steps; ++s) {
     if (periodic && (axes & 1))
@@ -108,6 +129,62 @@ static std::vector<double> serial_jacobi(int64_t ny, int64_t nx, int steps, bool
         if (source != 0) un[j * ld + i] += src[(j - 1) * nx + i - 1];
       }
     std::swap(u, un);
+  }
+  std::vector<double> out(ny * nx);
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) out[j * nx + i] = u[(j + 1) * ld + i + 1];
+  return out;
+}
+
+// Serial conjugate gradients on the whole Dirichlet problem, the definition of
+// JacobiSolver::cg (gmt/jacobi.hpp): `iters` iterations from the initial
+// field, the cell expressions in the kernels' order, the dot products summed
+// row by row.  *umax = max |u0| over the field and its ring.
+static std::vector<double> serial_cg(int64_t ny, int64_t nx, int iters, int source, double amp, uint64_t seed,
+                                     int init, double* umax) {
+  const int64_t ld = nx + 2;
+  std::vector<double> u = serial_init(ny, nx, init, seed), src;
+  if (source != 0) src = serial_source(ny, nx, source, amp, seed);
+  *umax = 0;
+  for (double v : u) *umax = std::fmax(*umax, std::fabs(v));
+  std::vector<double> r(u.size(), 0.0), p(u.size(), 0.0), q(u.size(), 0.0);
+  double rr = 0;
+  for (int64_t j = 1; j <= ny; ++j)
+    for (int64_t i = 1; i <= nx; ++i) {
+      const double* c = &u[j * ld + i];
+      double o = 0.25 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+      if (source != 0) o = o + 1.0 * src[(j - 1) * nx + i - 1];
+      const double d = o - c[0];
+      r[j * ld + i] = p[j * ld + i] = d;
+      rr += d * d;
+    }
+  for (int it = 0; it < iters; ++it) {
+    double pq = 0;
+    for (int64_t j = 1; j <= ny; ++j)
+      for (int64_t i = 1; i <= nx; ++i) {
+        const double* c = &p[j * ld + i];
+        const double v = c[0] - 0.25 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+        q[j * ld + i] = v;
+        pq += c[0] * v;
+      }
+    const double alpha = pq > 0 ? rr / pq : 0.0;
+    double rn = 0;
+    for (int64_t j = 1; j <= ny; ++j)
+      for (int64_t i = 1; i <= nx; ++i) {
+        const int64_t k = j * ld + i;
+        const double tp = alpha * p[k], tq = alpha * q[k];
+        u[k] = u[k] + tp;
+        r[k] = r[k] - tq;
+        rn += r[k] * r[k];
+      }
+    const double beta = rr > 0 ? rn / rr : 0.0;
+    for (int64_t j = 1; j <= ny; ++j)
+      for (int64_t i = 1; i <= nx; ++i) {
+        const int64_t k = j * ld + i;
+        const double t = beta * p[k];
+        p[k] = r[k] + t;
+      }
+    rr = rn;
   }
   std::vector<double> out(ny * nx);
   for (int64_t j = 0; j < ny; ++j)
@@ -162,6 +239,17 @@ int main(int argc, char** argv) {
     std::fflush(stdout);
     MPI_Abort(MPI_COMM_WORLD, 1);
   }
+  // --init=analytic|random, --seed=S
+  if (cli.has("init")) {
+    const std::string in = cli.get("init", "analytic");
+    c.init = in == "random" ? 1 : 0;
+    c.seed = static_cast<uint64_t>(cli.geti("seed", 0));
+    if (in != "analytic" && in != "random") {
+      if (rank == 0) std::printf("ERROR: --init=%s is not analytic or random\n", in.c_str());
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+  }
   // --source=poly | random[:AMP], --src-every=B
   const std::string src_arg = cli.get("source", "");
   if (!src_arg.empty()) {
@@ -187,7 +275,30 @@ int main(int argc, char** argv) {
   auto tr = comm::make_transport(comm::resolve(kind, b), MPI_COMM_WORLD, b);
 
   // solve to tolerance: --tol / --rtol
-  const bool solve_mode = cli.has("tol") || cli.has("rtol");
+  const bool cg_mode = cli.flag("cg");
+  const bool solve_mode = !cg_mode && (cli.has("tol") || cli.has("rtol"));
+  CgOpts co;
+  CgResult cr;
+  if (cg_mode) {
+    co.tol = std::atof(cli.get("tol", "0").c_str());
+    co.rtol = std::atof(cli.get("rtol", "0").c_str());
+    const std::string nm = cli.get("norm", "l2");
+    co.norm = nm == "max" ? 1 : 0;
+    co.lag = static_cast<int>(cli.geti("lag", 1));
+    co.check_every = static_cast<int>(cli.geti("check-every", 0));
+    if (co.check_every == 0) co.check_every = 10;
+    if (c.periodic || (nm != "l2" && nm != "max") || co.lag < 0 || co.lag > 8 || co.check_every < 1 || n_iter < 1 ||
+        !(co.tol >= 0) || !(co.rtol >= 0) || !std::isfinite(co.tol) || !std::isfinite(co.rtol)) {
+      if (rank == 0)
+        std::printf("ERROR: --cg needs Dirichlet sides (no --periodic: I - J is singular on a periodic axis), "
+                    "--tol and --rtol >= 0, --norm=l2|max, --lag=0..8, --check-every >= 1 and an iteration cap "
+                    "(n_iter) >= 1\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    co.max_iters = (n_iter + co.check_every - 1) / co.check_every * co.check_every;
+  }
+  const bool cg_fixed = cg_mode && !(co.tol > 0) && !(co.rtol > 0);
   SolveOpts so;
   SolveResult sr;
   double solve_ms = 0;
@@ -209,7 +320,7 @@ int main(int argc, char** argv) {
     }
   }
 
-  double t_step = 0, resid = 0, halo_us = 0, max_diff = -1;
+  double t_step = 0, resid = 0, halo_us = 0, max_diff = -1, check_bound = 1e-10;
   bool graph = false, overlap = false, band = false, push = false, graph_sweep = false, graph_fused = false;
   size_t hbytes = 0, hmsgs = 0;
   int64_t lnx = 0, lny = 0;
@@ -234,7 +345,23 @@ int main(int argc, char** argv) {
     lnx = solver.nx();
     lny = solver.ny();
     int total_sweeps = n_warmup + n_iter;  // what --check replays
-    if (solve_mode) {
+    if (cg_mode) {
+      // the warm-up runs one check's worth of iterations (first launches, the
+      // state of cg()), then the field is the initial one again
+      CgOpts w;
+      w.max_iters = w.check_every = co.check_every;
+      w.lag = 0;
+      solver.cg(w);
+      solver.prepare(1);
+      MPI_Barrier(MPI_COMM_WORLD);
+      const double t0 = wtime();
+      cr = solver.cg(co);
+      double dt = wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      solve_ms = dt * 1e3;
+      t_step = dt / (cr.iters > 0 ? cr.iters : 1);
+      total_sweeps = cr.iters;
+    } else if (solve_mode) {
       // the warm-up launches one pass of every kind and the residual kernel,
       // then the field is the initial one again: the solve starts from it
       if (so.check_every == 0) so.check_every = solver.tsteps();
@@ -276,11 +403,15 @@ int main(int argc, char** argv) {
       MPI_Gatherv(loc.data(), static_cast<int>(loc.size()), MPI_DOUBLE, g.data(), counts.data(),
                   displs.data(), MPI_DOUBLE, 0, MPI_COMM_WORLD);
       if (rank == 0) {
-        std::vector<double> ref = serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes,
-                                                c.source, c.source_amp, c.seed);
+        double umax = 0;
+        std::vector<double> ref =
+            cg_mode ? serial_cg(c.ny_global, c.nx_global, total_sweeps, c.source, c.source_amp, c.seed, c.init, &umax)
+                    : serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes, c.source,
+                                    c.source_amp, c.seed, c.init);
+        if (cg_mode) check_bound = 1e-10 * umax;
         // the poly source makes the initial field the discrete fixed point (fixed ring)
         std::vector<double> u0;
-        if (c.source == 1 && c.init == 0 && !c.periodic) {
+        if (c.source == 1 && c.init == 0 && !c.periodic && !cg_mode) {
           u0 = serial_jacobi(c.ny_global, c.nx_global, 0, c.periodic, c.periodic_axes);
           src_err = 0;
         }
@@ -313,7 +444,7 @@ int main(int argc, char** argv) {
       halo_us *= 1e6;
     }
     // solve mode: the deciding residual, without the extra sweep
-    resid = solve_mode ? sr.residual : solver.residual();
+    resid = cg_mode ? cr.residual : (solve_mode ? sr.residual : solver.residual());
   }
   if (rank == 0) {
     const double pts = static_cast<double>(c.ny_global) * c.nx_global;
@@ -341,7 +472,29 @@ int main(int argc, char** argv) {
         std::printf("source    = %s%s every 1 sweeps (set-up 0 sweeps, %0.3f ms, %0.1f MiB)\n",
                     c.source == 1 ? "poly" : "random", amp, src_setup_ms, src_mib);
     }
-    if (solve_mode) {
+    if (cg_mode) {
+      std::printf("solver    = cg\n");
+      if (cg_fixed)
+        std::printf("solve     = fixed count, %s norm, check every %d iterations\n", co.norm ? "max" : "l2",
+                    co.check_every);
+      else
+        std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d iterations, lag %d\n", co.tol, co.rtol,
+                    co.norm ? "max" : "l2", co.check_every, co.lag);
+      if (co.max_iters != cap_asked)
+        std::printf("steps     = at most %d (%d rounded up to a multiple of %d)\n", co.max_iters, cap_asked,
+                    co.check_every);
+      else
+        std::printf("steps     = at most %d\n", co.max_iters);
+      if (cg_fixed) {
+        std::printf("iters     : %d (fixed count, %d checks)\n", cr.iters, cr.checks);
+      } else {
+        std::printf("converged : %s%s\n", cr.converged ? "yes" : "no", cr.failed ? " (non-finite residual)" : "");
+        std::printf("iters     : %d (criterion met at %d, %d checks, lag %d)\n", cr.iters, cr.residual_iters, cr.checks,
+                    co.lag);
+      }
+      std::printf("TIME solve: %0.6f ms\n", solve_ms);
+      std::printf("TIME iter : %0.6f ms per iteration\n", t_step * 1e3);
+    } else if (solve_mode) {
       std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d sweeps, lag %d\n", so.tol, so.rtol,
                   so.norm ? "max" : "l2", so.check_every, so.lag);
       if (so.max_sweeps != cap_asked)
@@ -356,13 +509,19 @@ int main(int argc, char** argv) {
     } else {
       std::printf("steps     = %d (warmup %d)\n", n_iter, n_warmup);
     }
-    std::printf("TIME step : %0.6f ms\n", t_step * 1e3);
-    std::printf("MLUPS     : %0.1f (per GPU %0.1f, %0.1f GB/s per GPU at 16 B/pt)\n", mlups,
-                mlups / world, 16.0 * pts / world / t_step / 1e9);
+    if (!cg_mode) {
+      std::printf("TIME step : %0.6f ms\n", t_step * 1e3);
+      std::printf("MLUPS     : %0.1f (per GPU %0.1f, %0.1f GB/s per GPU at 16 B/pt)\n", mlups,
+                  mlups / world, 16.0 * pts / world / t_step / 1e9);
+    }
     if (halo_us > 0)
       std::printf("halo      : %0.2f us per exchange (%zu B, %zu msgs per rank)\n", halo_us, hbytes, hmsgs);
     std::printf("residual  : %.10e\n", resid);
-    if (max_diff >= 0)
+    if (cg_mode) std::printf("true resid: %.10e (max %.10e)\n", cr.true_residual, cr.true_residual_max);
+    if (max_diff >= 0 && cg_mode)
+      std::printf("check     : max|diff| vs serial cg = %.3e (bound %.3e) %s\n", max_diff, check_bound,
+                  max_diff <= check_bound ? "OK" : "FAIL");
+    else if (max_diff >= 0)
       std::printf("check     : max|diff| vs serial = %.3e %s\n", max_diff, max_diff < 1e-10 ? "OK" : "FAIL");
     if (src_err >= 0) std::printf("source err: max|u - u0| = %.3e\n", src_err);
     JsonRecord j;
@@ -374,6 +533,10 @@ int main(int argc, char** argv) {
     if (solve_mode)
       j.add("converged", sr.converged != 0).add("sweeps", sr.sweeps).add("residual_sweeps", sr.residual_sweeps)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
+    if (cg_mode)
+      j.add("solver", "cg").add("converged", cr.converged != 0).add("iters", cr.iters)
+          .add("residual_iters", cr.residual_iters).add("checks", cr.checks).add("solve_ms", solve_ms).add("r0", cr.r0)
+          .add("residual_max", cr.residual_max).add("true_residual", cr.true_residual);
     if (c.source != 0)
       j.add("source", c.source == 1 ? "poly" : "random").add("src_every", src_every > 0 ? src_every : 1)
           .add("source_setup_ms", src_setup_ms);
@@ -381,6 +544,9 @@ int main(int argc, char** argv) {
   }
   tr.reset();
   MPI_Finalize();
-  if (max_diff >= 1e-10) return 3;
+  // rank 0 ran the check: its verdict is every rank's exit status
+  int check_failed = cg_mode ? (max_diff > check_bound) : (max_diff >= 1e-10);
+  if (cg_mode) return check_failed ? 3 : (cr.failed || (!cg_fixed && !cr.converged) ? 4 : EXIT_SUCCESS);
+  if (check_failed) return 3;
   return solve_mode && (!sr.converged || sr.failed) ? 4 : EXIT_SUCCESS;
 }

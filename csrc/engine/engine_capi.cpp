@@ -220,6 +220,29 @@ int gmt_engine_jacobi_solve(void* p, const gmt_engine_solve_opts* o, gmt_engine_
   *out = {r.converged, r.sweeps, r.checks, r.residual_sweeps, r.residual, r.residual_max, r.r0, r.failed};
   return 0;
 }
+int gmt_engine_jacobi_cg(void* p, const gmt_engine_cg_opts* o, gmt_engine_cg_result* out) {
+  if (!p || !o || !out) return 1;
+  gmt::watchdog_kick("engine: jacobi cg");
+  auto& s = *static_cast<Handle*>(p)->s;
+  if (s.periodic()) return 2;
+  gmt::CgOpts co;
+  co.tol = o->tol;
+  co.rtol = o->rtol;
+  co.norm = o->norm;
+  co.max_iters = o->max_iters;
+  co.check_every = o->check_every;
+  co.lag = o->lag;
+  gmt::CgResult r;
+  try {
+    r = s.cg(co);
+  } catch (const std::invalid_argument&) {
+    return 1;
+  }
+  *out = {r.converged, r.iters,    r.checks,        r.residual_iters,    r.residual,
+          r.residual_max, r.r0, r.true_residual, r.true_residual_max, r.failed};
+  return 0;
+}
+int gmt_engine_jacobi_periodic(void* p) { return p && static_cast<Handle*>(p)->s->periodic() ? 1 : 0; }
 int gmt_engine_jacobi_exchange(void* p) {
   gmt::watchdog_kick("engine: halo exchange");
   static_cast<Handle*>(p)->s->exchange_only();

@@ -1058,13 +1058,16 @@ double JacobiSolver::residual() {
 // everything stream-ordered on s_, nothing waits.  The sum is followed by a
 // max over both values: whatever order a transport adds in, every rank then
 // holds the same two doubles and takes the same decision.
+void JacobiSolver::rn_setup() {
+  if (rn_dev_.data()) return;
+  rn_ws_ = Buffer<double>(static_cast<size_t>(gmt_jacobi5_resid_workspace(nx_, ny_)), GMT_SPACE_DEVICE);
+  rn_dev_ = Buffer<double>(2, GMT_SPACE_DEVICE);
+  rn_ring_ = Buffer<double>(2 * (kMaxLag + 1), GMT_SPACE_PINNED);
+  for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
+}
+
 void JacobiSolver::enqueue_residual() {
-  if (!rn_dev_.data()) {
-    rn_ws_ = Buffer<double>(static_cast<size_t>(gmt_jacobi5_resid_workspace(nx_, ny_)), GMT_SPACE_DEVICE);
-    rn_dev_ = Buffer<double>(2, GMT_SPACE_DEVICE);
-    rn_ring_ = Buffer<double>(2 * (kMaxLag + 1), GMT_SPACE_PINNED);
-    for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
-  }
+  rn_setup();
   if (!fresh_[parity_]) exchange_now(parity_);
   GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, src_f(), src_ld(), kC0,
                                                  src_c1(), rn_dev_.data(), rn_ws_.data(), s_));
@@ -1126,6 +1129,125 @@ SolveResult JacobiSolver::solve(const SolveOpts& o) {
   // the later checks' sweeps have run, an earlier check still decides)
   while (!stop && decided < res.checks) decide(decided++);
   synchronize();
+  return res;
+}
+
+// ---- conjugate gradients (gmt/jacobi.hpp CgOpts) ----
+
+void JacobiSolver::cg_setup() {
+  if (cg_sc_.data()) return;
+  watchdog_kick("jacobi: cg set-up");
+  const size_t elems = static_cast<size_t>(ld_) * (ny_ + 2 * g_);
+  Buffer<double>* fields[3] = {&cg_r_, &cg_p_, &cg_q_};
+  for (auto* b : fields) {
+    *b = Buffer<double>(elems, GMT_SPACE_DEVICE);
+    GMT_CHECK("memset", gmt_rt_memset_async(b->data(), 0, b->bytes(), s_));
+  }
+  cg_ws_ = Buffer<double>(static_cast<size_t>(gmt_cg_workspace(nx_, ny_)), GMT_SPACE_DEVICE);
+  cg_sc_ = Buffer<double>(6, GMT_SPACE_DEVICE);
+  GMT_CHECK("memset", gmt_rt_memset_async(cg_sc_.data(), 0, cg_sc_.bytes(), s_));
+  GMT_CHECK("cg set-up sync", gmt_rt_stream_synchronize(s_));
+  // the 1-wide ring of p around the interior: faces only, the plus-shaped
+  // stencil reads no corner
+  Neighbors nb = nb_;
+  nb.sw = nb.se = nb.nw = nb.ne = -2;
+  Span2D<double> f(cg_p_.data() + (yo_ - 1) * ld_ + (xo_ - 1), nx_ + 2, ny_ + 2, ld_);
+  cg_halo_ = std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, false);
+  rn_setup();
+  watchdog_kick("jacobi: cg ready");
+}
+
+// sum of [0], then max over both: whatever order a transport adds in, every
+// rank then holds the same two doubles (enqueue_residual's treatment)
+void JacobiSolver::cg_reduce(double* pair) {
+  t_.allreduce_sum(pair, 1, s_);
+  t_.allreduce_max(pair, 2, s_);
+}
+
+CgResult JacobiSolver::cg(const CgOpts& o) {
+  const int every = o.check_every == 0 ? 10 : o.check_every;
+  if (every < 1 || o.max_iters < 1 || o.max_iters % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
+      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !std::isfinite(o.tol) ||
+      !std::isfinite(o.rtol))
+    throw std::invalid_argument("JacobiSolver::cg: max_iters must be a positive multiple of check_every >= 1, "
+                                "0 <= lag <= 8, norm 0 or 1, tol and rtol finite and >= 0");
+  if (periodic())
+    throw std::invalid_argument("JacobiSolver::cg: I - J is singular on a periodic axis");
+  cg_setup();
+  const bool fixed = !(o.tol > 0.0) && !(o.rtol > 0.0);  // run exactly max_iters iterations
+  const int slots = o.lag + 1, last = o.max_iters / every;  // checks 0..last
+  double* u = buf_[parity_].data();
+  double* sc = cg_sc_.data();
+  CgResult res;
+  int decided = 0;
+  bool stop = false;
+  auto decide = [&](int i) {
+    GMT_CHECK("cg check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
+    watchdog_kick("jacobi cg check");
+    const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
+    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
+    res.residual_iters = i * every;
+    res.residual = r;
+    res.residual_max = mx;
+    if (i == 0) res.r0 = r;
+    if (!std::isfinite(sum) || !std::isfinite(mx)) {
+      res.failed = 1;
+      stop = true;
+    } else if (!fixed && r <= std::max(o.tol, o.rtol * res.r0)) {
+      res.converged = 1;
+      stop = true;
+    }
+  };
+  // iteration k reads rr from parity k & 1 and leaves rr' in the other slot
+  auto iterate = [&](int k) {
+    double* rr = sc + 2 * (k & 1);
+    double* rn = sc + 2 * ((k & 1) ^ 1);
+    double* pq = sc + 4;
+    if (cg_halo_->active()) {
+      cg_halo_->start(s_);
+      cg_halo_->finish(s_);
+    }
+    GMT_CHECK("cg apply", gmt_cg_apply(0, xo_, nx_, yo_, ny_, cg_p_.data(), ld_, nullptr, 0, kC0, 0.0, cg_q_.data(),
+                                       ld_, pq, cg_ws_.data(), s_));
+    cg_reduce(pq);
+    GMT_CHECK("cg update", gmt_cg_update(xo_, nx_, yo_, ny_, rr, pq, cg_p_.data(), ld_, cg_q_.data(), ld_, u, ld_,
+                                         cg_r_.data(), ld_, rn, cg_ws_.data(), s_));
+    cg_reduce(rn);
+    GMT_CHECK("cg direction", gmt_cg_dir(xo_, nx_, yo_, ny_, rn, rr, cg_r_.data(), ld_, cg_p_.data(), ld_, s_));
+  };
+  int k = 0;
+  for (int i = 0; i <= last && !stop; ++i) {
+    if (i == 0) {
+      // r = b - A u = the residual d of the current field; p = r on the interior
+      if (!fresh_[parity_]) exchange_now(parity_);
+      GMT_CHECK("cg residual", gmt_cg_apply(1, xo_, nx_, yo_, ny_, u, ld_, src_f(), src_ld(), kC0, src_c1(),
+                                            cg_r_.data(), ld_, sc, cg_ws_.data(), s_));
+      cg_reduce(sc);
+      const int64_t off = xo_ + yo_ * ld_;
+      const gmt_copy2d_desc d = {cg_r_.data() + off, cg_p_.data() + off, ld_, ld_, nx_, ny_};
+      GMT_CHECK("cg p = r", gmt_copy2d_batched(1, &d, sizeof(double), s_));
+    } else {
+      for (int j = 0; j < every; ++j) iterate(k++);
+      res.iters += every;
+      watchdog_kick("jacobi cg iterations enqueued");
+    }
+    GMT_CHECK("cg D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), sc + 2 * (k & 1), 2 * sizeof(double),
+                                            s_));
+    GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
+    res.checks = i + 1;
+    if (i >= o.lag) decide(decided++);
+  }
+  while (!stop && decided < res.checks) decide(decided++);
+  if (res.iters > 0) {
+    fresh_[parity_] = false;  // the ghost ring was not updated
+    advanced_ = true;
+  }
+  // the true residual of the final field beside the recursive one
+  enqueue_residual();
+  GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data(), rn_dev_.data(), 2 * sizeof(double), s_));
+  synchronize();
+  res.true_residual = std::sqrt(rn_ring_[0]);
+  res.true_residual_max = rn_ring_[1];
   return res;
 }
 

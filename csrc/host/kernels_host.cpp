@@ -322,6 +322,94 @@ int gmt_jacobi5_resid(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const doub
   return 0;
 }
 
+// the conjugate-gradient kernels (csrc/kernels/cg.hip): the same argument
+// checks and codes, the same cell arithmetic (this file is built with
+// -ffp-contract=off), row-major sums
+int64_t gmt_cg_workspace(int64_t, int64_t) { return 2; }
+int gmt_cg_apply_path(int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*,
+                      int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+int gmt_cg_update_path(int64_t, const double*, int64_t, const double*, int64_t, const double*, int64_t,
+                       const double*, int64_t) {
+  return GMT_PATH_NONE;
+}
+int gmt_cg_dir_path(int64_t, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+
+int gmt_cg_apply(int mode, int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* p, int64_t ldp,
+                 const double* f, int64_t ldf, double c0, double c1, double* q, int64_t ldq, double* out,
+                 double* ws, void*) {
+  if (!out || mode < 0 || mode > 1) return 1;
+  if (nx <= 0 || ny <= 0) {
+    out[0] = out[1] = 0.0;
+    return 0;
+  }
+  if (!p || !q || !ws || x0 < 1 || y0 < 1 || ldp < x0 + nx + 1 || ldq < x0 + nx) return 1;
+  if (mode == 0) f = nullptr;
+  if (f && ldf < x0 + nx) return 1;
+  double acc = 0.0, m = 0.0;
+  for (int64_t y = y0; y < y0 + ny; ++y)
+    for (int64_t x = x0; x < x0 + nx; ++x) {
+      const double* c = p + y * ldp + x;
+      double o = c0 * ((c[-1] + c[1]) + (c[-ldp] + c[ldp]));
+      double v;
+      if (mode == 0) {
+        v = c[0] - o;
+        acc += c[0] * v;
+      } else {
+        if (f) o = o + c1 * f[y * ldf + x];
+        v = o - c[0];
+        acc += v * v;
+        m = std::max(m, std::isnan(v) ? HUGE_VAL : std::fabs(v));
+      }
+      q[y * ldq + x] = v;
+    }
+  out[0] = acc;
+  out[1] = m;
+  return 0;
+}
+
+int gmt_cg_update(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* num, const double* den,
+                  const double* p, int64_t ldp, const double* q, int64_t ldq, double* x, int64_t ldx, double* r,
+                  int64_t ldr, double* out, double* ws, void*) {
+  if (!out) return 1;
+  if (nx <= 0 || ny <= 0) {
+    out[0] = out[1] = 0.0;
+    return 0;
+  }
+  if (!num || !den || !p || !q || !x || !r || !ws || x0 < 0 || y0 < 0 || ldp < x0 + nx || ldq < x0 + nx ||
+      ldx < x0 + nx || ldr < x0 + nx)
+    return 1;
+  const double a = *den > 0.0 ? *num / *den : 0.0;
+  double acc = 0.0, m = 0.0;
+  for (int64_t iy = y0; iy < y0 + ny; ++iy)
+    for (int64_t ix = x0; ix < x0 + nx; ++ix) {
+      const double tp = a * p[iy * ldp + ix], tq = a * q[iy * ldq + ix];
+      x[iy * ldx + ix] = x[iy * ldx + ix] + tp;
+      const double v = r[iy * ldr + ix] - tq;
+      r[iy * ldr + ix] = v;
+      acc += v * v;
+      m = std::max(m, std::isnan(v) ? HUGE_VAL : std::fabs(v));
+    }
+  out[0] = acc;
+  out[1] = m;
+  return 0;
+}
+
+int gmt_cg_dir(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* num, const double* den,
+               const double* r, int64_t ldr, double* p, int64_t ldp, void*) {
+  if (nx <= 0 || ny <= 0) return 0;
+  if (!num || !den || !r || !p || x0 < 0 || y0 < 0 || ldr < x0 + nx || ldp < x0 + nx) return 1;
+  const double b = *den > 0.0 ? *num / *den : 0.0;
+  for (int64_t iy = y0; iy < y0 + ny; ++iy)
+    for (int64_t ix = x0; ix < x0 + nx; ++ix) {
+      const double t = b * p[iy * ldp + ix];
+      p[iy * ldp + ix] = r[iy * ldr + ix] + t;
+    }
+  return 0;
+}
+
 int gmt_jacobi5_rects(int n_rect, const int64_t* r, const double* u, double* un, int64_t ld,
                       const double* f, int64_t ldf, double c0, double c1, void*) {
   if (n_rect > 4) return 1;

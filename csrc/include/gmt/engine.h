@@ -83,6 +83,26 @@ typedef struct gmt_engine_solve_result {
 } gmt_engine_solve_result;
 /* 0, or 1 on invalid options (nothing enqueued).  Collective. */
 int gmt_engine_jacobi_solve(void* h, const gmt_engine_solve_opts* opts, gmt_engine_solve_result* out);
+/* Conjugate gradients from the current field (JacobiSolver::cg, gmt/jacobi.hpp
+ * CgOpts / CgResult): the same criterion and lagged check; tol == rtol == 0
+ * runs exactly max_iters iterations. */
+typedef struct gmt_engine_cg_opts {
+  double tol, rtol;
+  int norm;        /* 0 L2, 1 max */
+  int max_iters;   /* a positive multiple of check_every */
+  int check_every; /* 0 = 10 */
+  int lag;         /* 0..8 */
+} gmt_engine_cg_opts;
+typedef struct gmt_engine_cg_result {
+  int converged, iters, checks, residual_iters;
+  double residual, residual_max, r0, true_residual, true_residual_max;
+  int failed; /* 1: a non-finite residual stopped the iteration */
+} gmt_engine_cg_result;
+/* 0; 1 on invalid options, 2 on an engine with a periodic axis (nothing
+ * enqueued either way).  Collective. */
+int gmt_engine_jacobi_cg(void* h, const gmt_engine_cg_opts* opts, gmt_engine_cg_result* out);
+/* 1 when the engine has a periodic axis */
+int gmt_engine_jacobi_periodic(void* h);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,
  * overlap_auto ns per pass with overlap, without (0 if not tuned), exact arithmetic in use,
  * band-first passes, inline halo exchange in use */

@@ -139,6 +139,30 @@ struct SolveResult {
   int failed = 0;           // 1: a non-finite residual stopped the solve
 };
 
+// JacobiSolver::cg: conjugate gradients on A u = b, A = I - J (J the Laplace
+// sweep; symmetric positive definite on a Dirichlet interior, the ring and the
+// source in b).  The residual r = b - A u is cell for cell the d of
+// residual_norm; the criterion and the lagged host check are solve()'s.
+struct CgOpts {
+  double tol = 0.0, rtol = 0.0;  // both 0: fixed-count mode, exactly max_iters iterations
+  int norm = 0;                  // 0: L2 (sqrt of the global sum of r^2), 1: max |r|
+  int max_iters = 0;             // the cap: a positive multiple of check_every
+  int check_every = 0;           // iterations between two checks (0 = 10)
+  int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
+};
+struct CgResult {
+  int converged = 0;        // the criterion was met
+  int iters = 0;            // iterations run: residual_iters + lag * check_every unless the cap came first
+  int checks = 0;           // checks enqueued
+  int residual_iters = 0;   // iteration count of the deciding check
+  double residual = 0.0;    // its (recursive) residual in the chosen norm,
+  double residual_max = 0.0;  // its max |r|,
+  double r0 = 0.0;          // and the residual of the starting field (chosen norm)
+  double true_residual = 0.0;      // residual_norm() of the final field: L2,
+  double true_residual_max = 0.0;  // and max
+  int failed = 0;           // 1: a non-finite residual stopped the iteration
+};
+
 class JacobiSolver {
  public:
   JacobiSolver(comm::Transport& t, const JacobiConfig& c);
@@ -167,6 +191,17 @@ class JacobiSolver {
   // idles for a check.  Every rank decides on the all-reduced values of the
   // same check.  Throws std::invalid_argument on bad options (nothing enqueued).
   SolveResult solve(const SolveOpts& o);
+  // Conjugate gradients from the current field, the solution updated in place
+  // (same buffer, same parity: run(k) afterwards keeps sweeping from it and
+  // captured graphs stay valid).  One iteration is a 1-wide halo exchange of
+  // the search direction, three kernels (gmt_cg_apply / _update / _dir, the
+  // step lengths computed on the device) and two all-reduces; check i is
+  // copied into the page-locked ring after i * check_every iterations and
+  // decided `lag` checks behind, as solve() does.  The first call builds the
+  // state (three fields, a halo plan: collective).  Throws
+  // std::invalid_argument on bad options or an engine with a periodic axis
+  // (A is singular there); nothing is enqueued then.
+  CgResult cg(const CgOpts& o);
   // one blocking halo exchange of the current field (latency measurements);
   // ordered after every pass already enqueued
   void exchange_only();
@@ -187,6 +222,7 @@ class JacobiSolver {
   // one block are plan_passes(src_every).
   void source_plan(int k, int out[3]) const;
   int source() const { return cfg_.source; }
+  bool periodic() const { return cfg_.periodic && (cfg_.periodic_axes & 3) != 0; }
   int src_every() const { return src_every_; }
   double max_abs_source() const { return smax_; }
   // sweeps and wall-clock ms of the last set-up of the block field; its and
@@ -268,6 +304,9 @@ class JacobiSolver {
   void split_cus();
   void setup_push();
   void enqueue_residual();  // {sum d^2, max |d|} over every rank into rn_dev_, stream-ordered on s_
+  void rn_setup();          // rn_ws_, rn_dev_, the ring and its events (first use)
+  void cg_setup();          // the state of cg() (first use; collective)
+  void cg_reduce(double* pair);  // all-reduce {sum, max} so every rank holds the same bits
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
   void push_pass(int parity, int k);   // the pass launch alone
@@ -308,6 +347,11 @@ class JacobiSolver {
   static constexpr int kMaxLag = 8;
   Buffer<double> rn_ws_, rn_dev_, rn_ring_;
   gmt_event_t rn_ev_[kMaxLag + 1] = {};
+  // cg(): residual, search direction and A p in buf_'s layout; the halo of p
+  // (width 1, faces only); the kernels' workspace; device scalars {sum, max}:
+  // rr by iteration parity at [0..1] and [2..3], p.q at [4..5]
+  Buffer<double> cg_r_, cg_p_, cg_q_, cg_ws_, cg_sc_;
+  std::unique_ptr<Halo2D> cg_halo_;
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values
   gmt_stream_t s_ = nullptr, cs_ = nullptr;

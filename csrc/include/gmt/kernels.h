@@ -220,6 +220,48 @@ int gmt_jacobi5_resid(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const doub
  * *seg_rows (may be NULL) = rows per segment of the row walk, 0 otherwise */
 int gmt_jacobi5_resid_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f,
                            int64_t ldf, int64_t* seg_rows);
+/* ---- Conjugate-gradient kernels (csrc/kernels/cg.hip) for A = I - J, J the
+ *      Laplace sweep above: the three launches of one CG iteration
+ *      (JacobiSolver::cg).  Conventions of gmt_jacobi5_resid: absolute x0, nx,
+ *      y0, ny, every field with its own pitch, asynchronous on `stream`.  Every
+ *      cell expression is evaluated without contraction, on both backends, so
+ *      given the same coefficient bits the fields are bitwise NumPy's; the
+ *      sums and maxima are deterministic (block partials, reduce_partials).
+ *      An empty region touches no field and sets out to {0, 0}.  Refused
+ *      (non-zero, the same on both backends): a NULL field, out, num, den or
+ *      workspace, a negative x0 or y0, x0 < 1 or y0 < 1 for apply, a
+ *      pitch shorter than the columns the call touches (x0 + nx, for apply's
+ *      input x0 + nx + 1), mode outside 0..1.  No cell outside the region is
+ *      written; apply reads only the region's plus-shaped set.
+ *      `workspace` must hold gmt_cg_workspace(nx, ny) doubles. */
+int64_t gmt_cg_workspace(int64_t nx, int64_t ny);
+/* mode 0: q = p - c0*((W+E)+(S+N)) of p, out = {sum p*q, 0} (f, ldf, c1 ignored)
+ * mode 1: q = c0*((W+E)+(S+N)) [+ c1*f] - p, bitwise gmt_jacobi5_resid's d,
+ *         out = {sum q^2, max |q| (NaN -> +inf)}; f may be NULL
+ * The row walk of the residual kernel with a store: 16 B per point. */
+int gmt_cg_apply(int mode, int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* p, int64_t ldp,
+                 const double* f, int64_t ldf, double c0, double c1, double* q, int64_t ldq,
+                 double* out /* 2 doubles */, double* workspace, void* stream);
+/* a = *den > 0 ? *num / *den : 0 (a NaN or non-positive denominator gives 0);
+ * x += a*p; r -= a*q; out = {sum r^2, max |r| (NaN -> +inf)} of the new r.
+ * num, den: device scalars.  48 B per point. */
+int gmt_cg_update(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* num, const double* den,
+                  const double* p, int64_t ldp, const double* q, int64_t ldq, double* x, int64_t ldx, double* r,
+                  int64_t ldr, double* out /* 2 doubles */, double* workspace, void* stream);
+/* b = *den > 0 ? *num / *den : 0; p = r + b*p.  24 B per point. */
+int gmt_cg_dir(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* num, const double* den,
+               const double* r, int64_t ldr, double* p, int64_t ldp, void* stream);
+/* The kernel each call would launch, nothing launched.  apply: GMT_PATH_ROW_WALK
+ * (x0 even, every pointer 16-B aligned, every pitch even; *seg_rows, may be
+ * NULL, = rows per segment) or GMT_PATH_SCALAR (*seg_rows = 0); f counts only
+ * when non-NULL.  update / dir: GMT_PATH_PT (column pairs under the same rule;
+ * an odd nx keeps it with a scalar last column) or GMT_PATH_SCALAR. */
+int gmt_cg_apply_path(int64_t x0, int64_t nx, int64_t ny, const double* p, int64_t ldp, const double* f,
+                      int64_t ldf, const double* q, int64_t ldq, int64_t* seg_rows);
+int gmt_cg_update_path(int64_t x0, const double* p, int64_t ldp, const double* q, int64_t ldq, const double* x,
+                       int64_t ldx, const double* r, int64_t ldr);
+int gmt_cg_dir_path(int64_t x0, const double* r, int64_t ldr, const double* p, int64_t ldp);
+
 /* ---- Temporal-blocking Jacobi (csrc/kernels/jacobi5tb.hip): `sweeps` fused
  *      Laplace sweeps per memory pass, un = J^sweeps(u), on up to 8 output
  *      rects {x0, nx, y0, ny} (absolute array coordinates, x0 >= sweeps,

@@ -155,6 +155,19 @@ _SIGS = {
         [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_vp, c_vp],
     ),
     "gmt_jacobi5_resid_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_cg_workspace": (c_i64, [c_i64, c_i64]),
+    "gmt_cg_apply": (
+        c_int,
+        [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp],
+    ),
+    "gmt_cg_update": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp],
+    ),
+    "gmt_cg_dir": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_cg_apply_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_cg_update_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "gmt_cg_dir_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
     "gmt_jacobi5_rects": (
         c_int,
         [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp],

@@ -25,6 +25,7 @@ binding the wrong one.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -67,7 +68,22 @@ class SolveResult(ctypes.Structure):
                 ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("failed", ctypes.c_int)]
 
 
+class CgOpts(ctypes.Structure):
+    """gmt_engine_cg_opts (csrc/include/gmt/engine.h)."""
+    _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
+                ("max_iters", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int)]
+
+
+class CgResult(ctypes.Structure):
+    """gmt_engine_cg_result (csrc/include/gmt/engine.h)."""
+    _fields_ = [("converged", ctypes.c_int), ("iters", ctypes.c_int), ("checks", ctypes.c_int),
+                ("residual_iters", ctypes.c_int), ("residual", ctypes.c_double),
+                ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("true_residual", ctypes.c_double),
+                ("true_residual_max", ctypes.c_double), ("failed", ctypes.c_int)]
+
+
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
+CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
 
 
@@ -118,6 +134,10 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_residual_norm.restype = c_int
     lib.gmt_engine_jacobi_solve.argtypes = [vp, ctypes.POINTER(SolveOpts), ctypes.POINTER(SolveResult)]
     lib.gmt_engine_jacobi_solve.restype = c_int
+    lib.gmt_engine_jacobi_cg.argtypes = [vp, ctypes.POINTER(CgOpts), ctypes.POINTER(CgResult)]
+    lib.gmt_engine_jacobi_cg.restype = c_int
+    lib.gmt_engine_jacobi_periodic.argtypes = [vp]
+    lib.gmt_engine_jacobi_periodic.restype = c_int
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
     lib.gmt_engine_jacobi_info.restype = c_int
     lib.gmt_engine_jacobi_graphs.argtypes = [vp]
@@ -543,6 +563,46 @@ class NativeJacobi:
             raise ValueError("gmt_engine_jacobi_solve rejected its options")
         return {n: getattr(r, n) for n, _ in SolveResult._fields_}
 
+    def cg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_iters: int = 0,
+           check_every: int = 0, lag: int = 1) -> dict:
+        """Conjugate gradients on ``(I - J) u = b`` from the current field until
+        the residual meets ``r <= max(tol, rtol * r0)`` in ``norm`` ("l2" or
+        "max"; r0: the residual of the starting field) or ``max_iters``
+        iterations have run (JacobiSolver::cg).  The residual is the same
+        ``d = J(u) [+ s] - u`` as :meth:`residual_norm`'s, carried by the CG
+        recurrence; it is checked every ``check_every`` iterations (0 = 10)
+        and the host decides ``lag`` checks behind the device, so with
+        lag >= 1 an iteration never waits for the host.  ``tol == rtol == 0``
+        runs exactly ``max_iters`` iterations (``converged`` stays 0).  The
+        solution replaces the current field in place; :meth:`run` afterwards
+        keeps sweeping from it.  Returns the fields of CgResult:
+        ``converged``, ``iters`` (``residual_iters + lag * check_every``
+        unless the cap came first), ``checks``, ``residual_iters`` (the
+        deciding check's), ``residual``, ``residual_max``, ``r0``,
+        ``true_residual`` / ``true_residual_max`` (:meth:`residual_norm` of
+        the final field), ``failed`` (a non-finite residual).  Identical on
+        every rank.  Dirichlet engines only: a periodic axis raises
+        ValueError.  Collective."""
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
+        every = int(check_every) if check_every else CG_CHECK_EVERY
+        if isinstance(lag, bool) or not 0 <= int(lag) <= MAX_LAG:
+            raise ValueError(f"lag must be 0..{MAX_LAG}, got {lag!r}")
+        if every < 1:
+            raise ValueError(f"check_every must be >= 1 (0 = {CG_CHECK_EVERY}), got {check_every!r}")
+        if int(max_iters) < 1 or int(max_iters) % every:
+            raise ValueError(f"max_iters must be a positive multiple of check_every ({every}), got {max_iters!r}")
+        tol, rtol = float(tol), float(rtol)
+        if not (np.isfinite(tol) and np.isfinite(rtol)) or tol < 0 or rtol < 0:
+            raise ValueError("tol and rtol must be finite and >= 0")
+        if self.lib.gmt_engine_jacobi_periodic(self.h):
+            raise ValueError("cg needs Dirichlet sides: I - J is singular on a periodic axis")
+        o = CgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_iters=int(max_iters), check_every=every, lag=int(lag))
+        r = CgResult()
+        if self.lib.gmt_engine_jacobi_cg(self.h, ctypes.byref(o), ctypes.byref(r)):
+            raise ValueError("gmt_engine_jacobi_cg rejected its options")
+        return {n: getattr(r, n) for n, _ in CgResult._fields_}
+
     def interior(self) -> np.ndarray:
         out = np.empty((self.ny, self.nx), dtype=np.float64)
         self.lib.gmt_engine_jacobi_copy_interior(self.h, out.ctypes.data)
@@ -750,3 +810,44 @@ def serial_jacobi(ny: int, nx: int, steps: int, periodic: bool = False, init: st
             un[1:-1, 1:-1] += s
         u, un = un, u
     return u[1:-1, 1:-1].copy()
+
+
+def serial_cg(ny: int, nx: int, iters: int, init: str = "analytic", seed: int = 0,
+              source: "str | np.ndarray | None" = None, source_amp: float = 1.0, keep=None):
+    """NumPy definition of :meth:`NativeJacobi.cg` on the whole Dirichlet
+    problem: ``iters`` conjugate-gradient iterations on ``(I - J) u = b`` from
+    the engine's initial field, every cell expression in the kernels' operation
+    order, the dot products by ``math.fsum``.  Returns ``(field, series)``:
+    the ny x nx interior after the last iteration and the list of
+    ``(sqrt(rr), max |r|)`` of the recursive residual, entry k after k
+    iterations (entry 0: the starting field's).  With ``keep`` (iteration
+    counts), ``field`` is instead the dict ``{k: interior after k iterations}``
+    of those counts: one run serves every count a test compares at."""
+    u = initial_field(ny, nx, init, seed)
+    s = None if source is None else source_field(ny, nx, source, seed, source_amp)
+    c = u[1:-1, 1:-1]
+    o = 0.25 * ((u[1:-1, :-2] + u[1:-1, 2:]) + (u[:-2, 1:-1] + u[2:, 1:-1]))
+    if s is not None:
+        o = o + 1.0 * s
+    r = o - c
+    fsum = lambda a: math.fsum(a.ravel().tolist())  # noqa: E731
+    rr = fsum(r * r)
+    series = [(math.sqrt(rr), float(np.abs(r).max()))]
+    p = np.zeros_like(u)
+    p[1:-1, 1:-1] = r
+    pc = p[1:-1, 1:-1]
+    kept = {0: c.copy()} if keep is not None and 0 in keep else {}
+    for it in range(iters):
+        q = pc - 0.25 * ((p[1:-1, :-2] + p[1:-1, 2:]) + (p[:-2, 1:-1] + p[2:, 1:-1]))
+        pq = fsum(pc * q)
+        alpha = rr / pq if pq > 0 else 0.0
+        c += alpha * pc
+        r -= alpha * q
+        rr_new = fsum(r * r)
+        series.append((math.sqrt(rr_new), float(np.abs(r).max())))
+        beta = rr_new / rr if rr > 0 else 0.0
+        pc[...] = r + beta * pc
+        rr = rr_new
+        if keep is not None and it + 1 in keep:
+            kept[it + 1] = c.copy()
+    return (c.copy() if keep is None else kept), series

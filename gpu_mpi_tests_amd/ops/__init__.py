@@ -5,13 +5,20 @@ K4/K5/K11 ``stencil5_2d`` (and its ``stencil5_2d_edges`` /
 ``stencil5_2d_interior`` split for overlapped steps); K6/K7/K8 ``copy2d_batched`` (halo pack/unpack);
 K9 ``sum_axis``; K10/K12 ``diff_sq``/``diff_norm``; analytic ``fill_poly``;
 and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
-its read-only residual ``jacobi5_resid``
+its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
+``cg_apply`` / ``cg_update`` / ``cg_dir``
 and ``jacobi5tb`` (K fused sweeps per memory pass).
 """
 from .kernels import (  # noqa: F401
     abs_max,
     add2d,
     add2d_path,
+    cg_apply,
+    cg_apply_path,
+    cg_dir,
+    cg_dir_path,
+    cg_update,
+    cg_update_path,
     copy2d_batched,
     daxpy,
     diff_norm,

@@ -447,6 +447,91 @@ def jacobi5_resid_path(u: torch.Tensor, region: tuple[int, int, int, int],
     return int(path), int(seg.value)
 
 
+def _ptr_ld(t: "torch.Tensor | None") -> tuple[int, int]:
+    return (t.data_ptr(), t.stride(0)) if t is not None else (0, 0)
+
+
+def cg_apply(p: torch.Tensor, q: torch.Tensor, region: tuple[int, int, int, int], mode: int = 0,
+             f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> torch.Tensor:
+    """The operator launch of a conjugate-gradient iteration over
+    ``region = (x0, nx, y0, ny)`` (gmt_cg_apply), written to ``q``.
+    mode 0: ``q = p - c0*((W + E) + (S + N))`` of ``p``, returns
+    ``(sum p*q, 0)``; mode 1: ``q = c0*((W + E) + (S + N)) [+ c1*f] - p``
+    (bitwise :func:`jacobi5_resid`'s d), returns ``(sum q^2, max |q|)`` with a
+    NaN counted as ``+inf``.  No contraction: ``q`` is bitwise NumPy's."""
+    _check2d(p, "cg_apply.p")
+    _check2d(q, "cg_apply.q")
+    if f is not None:
+        _check2d(f, "cg_apply.f")
+    x0, nx, y0, ny = (int(v) for v in region)
+    if not _is_dev(p):
+        return ref.cg_apply(p, q, x0, nx, y0, ny, mode, f, c0, c1)
+    L = _native.lib()
+    ws = torch.empty(max(2, L.gmt_cg_workspace(nx, ny)), dtype=torch.float64, device=p.device)
+    out = torch.empty(2, dtype=torch.float64, device=p.device)
+    _native.check(L.gmt_cg_apply(int(mode), x0, nx, y0, ny, p.data_ptr(), p.stride(0), *_ptr_ld(f), float(c0),
+                                 float(c1), q.data_ptr(), q.stride(0), out.data_ptr(), ws.data_ptr(), _stream(p)),
+                  "gmt_cg_apply")
+    return out
+
+
+def cg_update(num: torch.Tensor, den: torch.Tensor, p: torch.Tensor, q: torch.Tensor, x: torch.Tensor,
+              r: torch.Tensor, region: tuple[int, int, int, int]) -> torch.Tensor:
+    """``a = den > 0 ? num / den : 0`` from the one-element tensors ``num`` and
+    ``den`` (read on the device); ``x += a*p``; ``r -= a*q`` over ``region``
+    (gmt_cg_update).  Returns ``(sum r^2, max |r|)`` of the new ``r`` (NaN
+    counted as ``+inf``)."""
+    for t, n in ((p, "p"), (q, "q"), (x, "x"), (r, "r")):
+        _check2d(t, "cg_update." + n)
+    x0, nx, y0, ny = (int(v) for v in region)
+    if not _is_dev(x):
+        return ref.cg_update(num, den, p, q, x, r, x0, nx, y0, ny)
+    L = _native.lib()
+    ws = torch.empty(max(2, L.gmt_cg_workspace(nx, ny)), dtype=torch.float64, device=x.device)
+    out = torch.empty(2, dtype=torch.float64, device=x.device)
+    _native.check(L.gmt_cg_update(x0, nx, y0, ny, num.data_ptr(), den.data_ptr(), p.data_ptr(), p.stride(0),
+                                  q.data_ptr(), q.stride(0), x.data_ptr(), x.stride(0), r.data_ptr(), r.stride(0),
+                                  out.data_ptr(), ws.data_ptr(), _stream(x)), "gmt_cg_update")
+    return out
+
+
+def cg_dir(num: torch.Tensor, den: torch.Tensor, r: torch.Tensor, p: torch.Tensor,
+           region: tuple[int, int, int, int]) -> torch.Tensor:
+    """``b = den > 0 ? num / den : 0``; ``p = r + b*p`` over ``region``
+    (gmt_cg_dir), in place; returns ``p``."""
+    _check2d(r, "cg_dir.r")
+    _check2d(p, "cg_dir.p")
+    x0, nx, y0, ny = (int(v) for v in region)
+    if not _is_dev(p):
+        return ref.cg_dir(num, den, r, p, x0, nx, y0, ny)
+    _native.check(_native.lib().gmt_cg_dir(x0, nx, y0, ny, num.data_ptr(), den.data_ptr(), r.data_ptr(),
+                                           r.stride(0), p.data_ptr(), p.stride(0), _stream(p)), "gmt_cg_dir")
+    return p
+
+
+def cg_apply_path(p: torch.Tensor, q: torch.Tensor, region: tuple[int, int, int, int],
+                  f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`cg_apply` would launch (gmt_cg_apply_path, no launch):
+    ``(PATH_ROW_WALK or PATH_SCALAR, rows per segment of the row walk)``."""
+    x0, nx, _, ny = (int(v) for v in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_cg_apply_path(x0, nx, ny, p.data_ptr(), p.stride(0), *_ptr_ld(f), q.data_ptr(),
+                                           q.stride(0), ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def cg_update_path(p: torch.Tensor, q: torch.Tensor, x: torch.Tensor, r: torch.Tensor,
+                   region: tuple[int, int, int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`cg_update` would launch (no launch)."""
+    return int(_native.lib().gmt_cg_update_path(int(region[0]), p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0),
+                                                x.data_ptr(), x.stride(0), r.data_ptr(), r.stride(0)))
+
+
+def cg_dir_path(r: torch.Tensor, p: torch.Tensor, region: tuple[int, int, int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`cg_dir` would launch (no launch)."""
+    return int(_native.lib().gmt_cg_dir_path(int(region[0]), r.data_ptr(), r.stride(0), p.data_ptr(), p.stride(0)))
+
+
 def jacobi5_rects(u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],
                   f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> None:
     """Sweep up to 4 rectangles (the boundary frame of an overlapped step) in one launch."""

@@ -103,6 +103,58 @@ def jacobi5_resid(u: torch.Tensor, x0: int, nx: int, y0: int, ny: int, f: torch.
     return torch.stack(((d * d).sum(), d.abs().nan_to_num(nan=float("inf")).max()))
 
 
+def _nan_inf_max(v: torch.Tensor) -> torch.Tensor:
+    return v.abs().nan_to_num(nan=float("inf")).max()
+
+
+def cg_apply(p: torch.Tensor, q: torch.Tensor, x0: int, nx: int, y0: int, ny: int, mode: int = 0,
+             f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> torch.Tensor:
+    """gmt_cg_apply: q over the region, and (sum p*q, 0) (mode 0) or (sum q^2, max |q|) (mode 1)."""
+    if mode not in (0, 1):
+        raise ValueError(f"cg_apply: mode must be 0 or 1, got {mode!r}")
+    if nx <= 0 or ny <= 0:
+        return torch.zeros(2, dtype=p.dtype, device=p.device)
+    ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+    o = c0 * ((p[ys, x0 - 1 : x0 - 1 + nx] + p[ys, x0 + 1 : x0 + 1 + nx])
+              + (p[y0 - 1 : y0 - 1 + ny, xs] + p[y0 + 1 : y0 + 1 + ny, xs]))
+    c = p[ys, xs]
+    if mode == 0:
+        v = c - o
+        q[ys, xs] = v
+        return torch.stack(((c * v).sum(), torch.zeros((), dtype=p.dtype, device=p.device)))
+    if f is not None:
+        o = o + c1 * f[ys, xs]
+    v = o - c
+    q[ys, xs] = v
+    return torch.stack(((v * v).sum(), _nan_inf_max(v)))
+
+
+def _cg_coef(num: torch.Tensor, den: torch.Tensor) -> float:
+    n, d = float(num.reshape(-1)[0]), float(den.reshape(-1)[0])
+    return n / d if d > 0 else 0.0
+
+
+def cg_update(num, den, p, q, x, r, x0: int, nx: int, y0: int, ny: int) -> torch.Tensor:
+    """gmt_cg_update: x += a*p, r -= a*q over the region; (sum r^2, max |r|) of the new r."""
+    if nx <= 0 or ny <= 0:
+        return torch.zeros(2, dtype=x.dtype, device=x.device)
+    a = _cg_coef(num, den)
+    ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+    x[ys, xs] = x[ys, xs] + a * p[ys, xs]
+    v = r[ys, xs] - a * q[ys, xs]
+    r[ys, xs] = v
+    return torch.stack(((v * v).sum(), _nan_inf_max(v)))
+
+
+def cg_dir(num, den, r, p, x0: int, nx: int, y0: int, ny: int) -> torch.Tensor:
+    """gmt_cg_dir: p = r + b*p over the region."""
+    if nx > 0 and ny > 0:
+        b = _cg_coef(num, den)
+        ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+        p[ys, xs] = r[ys, xs] + b * p[ys, xs]
+    return p
+
+
 def jacobi5xk(k: int, u: torch.Tensor, un: torch.Tensor, rects, dom, halo_mask: int = 0) -> None:
     """fp64 reference of k fused Laplace sweeps with the ghost-side rule of
     csrc/kernels/jacobi5tb.hip: a ring cell outside ``dom`` gets an
