@@ -15,6 +15,8 @@
 //      the sweep with residual (16 B/point) and gmt_sum, at 8192^2 and 32768^2
 //      --only=add2d [--reps=5]: the source-block add (gmt_add2d) alternated with
 //      gmt_daxpy on the same element count (24 B/point each)
+//      --only=cheby [--reps=5] [--cheby-n=N]: the launch of a Chebyshev iteration
+//      (gmt_cheby_step, 24 B/point, 32 with f) against gmt_daxpy, as --only=cg.
 //      --only=cg [--reps=5] [--cg-n=N]: the three launches of a conjugate-gradient
 //      iteration (gmt_cg_apply 16 B/point, gmt_cg_update 48, gmt_cg_dir 24), each
 //      alternated with gmt_daxpy on the same element count
@@ -441,6 +443,55 @@ int main(int argc, char** argv) {
       report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
       report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
       std::printf("cg %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
+                  (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
+    }
+  }
+  if (only.find("cheby") != std::string::npos) {
+    // --only=cheby: the launch of a JacobiSolver::cheby iteration
+    // (gmt_cheby_step) in the engine's layout (interior at column 8, pitch
+    // padded to 64) at 8192^2, without and with f, each against gmt_daxpy on
+    // n * n contiguous elements, --reps=5 rounds in the order A B B A; the
+    // best of the rounds is compared.  GB/s from the compulsory bytes: 24 B
+    // per point, 32 with f.
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    const int64_t n = cli.geti("cheby-n", 8192);
+    const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64;
+    const size_t elems = static_cast<size_t>(ld) * (n + 2);
+    Buffer<double> u(elems, GMT_SPACE_DEVICE), v(elems, GMT_SPACE_DEVICE), f(elems, GMT_SPACE_DEVICE);
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, u.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, v.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(3, ld, n + 2, 0.0, 1e-9, 0.0, 0.0, f.data(), ld, s));
+    GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+    int64_t seg = 0, segf = 0;
+    const int path = gmt_cheby_step_path(xo, n, n, u.data(), ld, nullptr, 0, v.data(), ld, &seg);
+    const int pathf = gmt_cheby_step_path(xo, n, n, u.data(), ld, f.data(), ld, v.data(), ld, &segf);
+    std::printf("cheby %lldx%lld  path %d (%lld rows per segment), with f %d (%lld), pitch %lld\n", (long long)n,
+                (long long)n, path, (long long)seg, pathf, (long long)segf, (long long)ld);
+    // w = 0.5: v converges to G(u), the fields stay bounded over the repeats
+    const std::function<void()> kernel[2] = {
+        [&] { GMT_CHECK("cheby_step", gmt_cheby_step(xo, n, 1, n, u.data(), ld, nullptr, 0, 0.25, 0.0, 0.5, v.data(),
+                                                     ld, s)); },
+        [&] { GMT_CHECK("cheby_step_f", gmt_cheby_step(xo, n, 1, n, u.data(), ld, f.data(), ld, 0.25, 1.0, 0.5,
+                                                       v.data(), ld, s)); }};
+    const std::function<void()> daxpy = [&] { GMT_CHECK("daxpy", gmt_daxpy(n * n, 1e-3, f.data(), u.data(), s)); };
+    const char* name[2] = {"cheby_step", "cheby_step_f"};
+    const double bytes[2] = {24.0, 32.0};
+    for (int k = 0; k < 2; ++k) {
+      Stats st[2];
+      const int order[4] = {0, 1, 1, 0};
+      for (int rep = 0; rep < reps; ++rep)
+        for (int o = 0; o < 4; ++o) {
+          const int w = order[o];
+          const double ms = time_ms(s, iters, w == 0 ? kernel[k] : daxpy);
+          st[w].add(ms);
+          std::printf("cheby %lldx%lld rep %d  %-12s %9.4f ms\n", (long long)n, (long long)n, rep,
+                      w == 0 ? name[k] : "daxpy", ms);
+        }
+      char shape[64];
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+      report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
+      report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
+      std::printf("cheby %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
                   (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
     }
   }

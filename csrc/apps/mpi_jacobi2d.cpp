@@ -51,6 +51,13 @@
 //                           runs the same number of iterations of the serial whole-problem CG and
 //                           compares within 1e-10 * max|u0| (dot products depend on the
 //                           decomposition: not bitwise)
+//   --cheby [--rho=R]       Chebyshev semi-iteration over the sweep instead of sweeps
+//                           (JacobiSolver::cheby; Dirichlet only, exclusive with --cg): the options
+//                           of --cg; R the spectral radius of the sweep, finite and in (0, 1)
+//                           (default: the closed form of the global interior; an over-estimate
+//                           converges more slowly, an under-estimate can stagnate).  --check runs
+//                           the same number of serial Chebyshev iterations with the same rho and
+//                           compares within 1e-10 * max|u0|
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -192,6 +199,44 @@ static std::vector<double> serial_cg(int64_t ny, int64_t nx, int iters, int sour
   return out;
 }
 
+// Serial Chebyshev semi-iteration on the whole Dirichlet problem, the
+// definition of JacobiSolver::cheby (gmt/jacobi.hpp): `iters` iterations from
+// the initial field with the weights of `rho`, the cell in the kernel's order.
+// *umax = max |u0| over the field and its ring.
+static std::vector<double> serial_cheby(int64_t ny, int64_t nx, int iters, double rho, int source, double amp,
+                                        uint64_t seed, int init, double* umax) {
+  const int64_t ld = nx + 2;
+  std::vector<double> u = serial_init(ny, nx, init, seed), src;
+  if (source != 0) src = serial_source(ny, nx, source, amp, seed);
+  *umax = 0;
+  for (double v : u) *umax = std::fmax(*umax, std::fabs(v));
+  std::vector<double> v = u;
+  const double rho2 = rho * rho;
+  double w = 1.0;
+  for (int it = 0; it < iters; ++it) {
+    if (it > 0) w = cheby_next_weight(rho2, w, it);
+    for (int64_t j = 1; j <= ny; ++j)
+      for (int64_t i = 1; i <= nx; ++i) {
+        const double* c = &u[j * ld + i];
+        double o = 0.25 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+        if (source != 0) o = o + 1.0 * src[(j - 1) * nx + i - 1];
+        if (it == 0) {
+          v[j * ld + i] = o;
+        } else {
+          const double pv = v[j * ld + i];
+          volatile double t = o - pv;  // each operation rounded once
+          t = w * t;
+          v[j * ld + i] = pv + t;
+        }
+      }
+    std::swap(u, v);
+  }
+  std::vector<double> out(ny * nx);
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) out[j * nx + i] = u[(j + 1) * ld + i + 1];
+  return out;
+}
+
 int main(int argc, char** argv) {
   Cli cli(argc, argv);
   int64_t n = cli.positional(0) ? std::atoll(cli.positional(0)) : 8192;
@@ -275,10 +320,29 @@ int main(int argc, char** argv) {
   auto tr = comm::make_transport(comm::resolve(kind, b), MPI_COMM_WORLD, b);
 
   // solve to tolerance: --tol / --rtol
-  const bool cg_mode = cli.flag("cg");
+  // cg_mode covers both Krylov-rate modes (their options, timing and report
+  // are shared); cheby_mode picks JacobiSolver::cheby
+  const bool cheby_mode = cli.flag("cheby");
+  if (cheby_mode && cli.flag("cg")) {
+    if (rank == 0) std::printf("ERROR: --cheby and --cg are exclusive\n");
+    std::fflush(stdout);
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
+  const bool cg_mode = cli.flag("cg") || cheby_mode;
+  const char* mode_name = cheby_mode ? "--cheby" : "--cg";
   const bool solve_mode = !cg_mode && (cli.has("tol") || cli.has("rtol"));
   CgOpts co;
   CgResult cr;
+  ChebyOpts ho;
+  double rho_used = 0;
+  if (cheby_mode) {
+    ho.rho = std::atof(cli.get("rho", "0").c_str());
+    if (cli.has("rho") && !(std::isfinite(ho.rho) && ho.rho > 0 && ho.rho < 1)) {
+      if (rank == 0) std::printf("ERROR: --rho must be finite and in (0, 1)\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+  }
   if (cg_mode) {
     co.tol = std::atof(cli.get("tol", "0").c_str());
     co.rtol = std::atof(cli.get("rtol", "0").c_str());
@@ -290,13 +354,19 @@ int main(int argc, char** argv) {
     if (c.periodic || (nm != "l2" && nm != "max") || co.lag < 0 || co.lag > 8 || co.check_every < 1 || n_iter < 1 ||
         !(co.tol >= 0) || !(co.rtol >= 0) || !std::isfinite(co.tol) || !std::isfinite(co.rtol)) {
       if (rank == 0)
-        std::printf("ERROR: --cg needs Dirichlet sides (no --periodic: I - J is singular on a periodic axis), "
+        std::printf("ERROR: %s needs Dirichlet sides (no --periodic: I - J is singular on a periodic axis), "
                     "--tol and --rtol >= 0, --norm=l2|max, --lag=0..8, --check-every >= 1 and an iteration cap "
-                    "(n_iter) >= 1\n");
+                    "(n_iter) >= 1\n", mode_name);
       std::fflush(stdout);
       MPI_Abort(MPI_COMM_WORLD, 1);
     }
     co.max_iters = (n_iter + co.check_every - 1) / co.check_every * co.check_every;
+    ho.tol = co.tol;
+    ho.rtol = co.rtol;
+    ho.norm = co.norm;
+    ho.lag = co.lag;
+    ho.check_every = co.check_every;
+    ho.max_iters = co.max_iters;
   }
   const bool cg_fixed = cg_mode && !(co.tol > 0) && !(co.rtol > 0);
   SolveOpts so;
@@ -345,7 +415,33 @@ int main(int argc, char** argv) {
     lnx = solver.nx();
     lny = solver.ny();
     int total_sweeps = n_warmup + n_iter;  // what --check replays
-    if (cg_mode) {
+    if (cheby_mode) {
+      // the warm-up as for --cg below: one check's worth of iterations (first
+      // launches, the halo plans), then the field is the initial one again
+      ChebyOpts w;
+      w.max_iters = w.check_every = ho.check_every;
+      w.lag = 0;
+      w.rho = ho.rho;
+      solver.cheby(w);
+      solver.prepare(1);
+      MPI_Barrier(MPI_COMM_WORLD);
+      const double t0 = wtime();
+      const ChebyResult hr = solver.cheby(ho);
+      double dt = wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      solve_ms = dt * 1e3;
+      t_step = dt / (hr.iters > 0 ? hr.iters : 1);
+      total_sweeps = hr.iters;
+      rho_used = hr.rho;
+      cr.converged = hr.converged;
+      cr.iters = hr.iters;
+      cr.checks = hr.checks;
+      cr.residual_iters = hr.residual_iters;
+      cr.residual = hr.residual;
+      cr.residual_max = hr.residual_max;
+      cr.r0 = hr.r0;
+      cr.failed = hr.failed;
+    } else if (cg_mode) {
       // the warm-up runs one check's worth of iterations (first launches, the
       // state of cg()), then the field is the initial one again
       CgOpts w;
@@ -405,7 +501,9 @@ int main(int argc, char** argv) {
       if (rank == 0) {
         double umax = 0;
         std::vector<double> ref =
-            cg_mode ? serial_cg(c.ny_global, c.nx_global, total_sweeps, c.source, c.source_amp, c.seed, c.init, &umax)
+            cheby_mode ? serial_cheby(c.ny_global, c.nx_global, total_sweeps, rho_used, c.source, c.source_amp,
+                                      c.seed, c.init, &umax)
+            : cg_mode ? serial_cg(c.ny_global, c.nx_global, total_sweeps, c.source, c.source_amp, c.seed, c.init, &umax)
                     : serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes, c.source,
                                     c.source_amp, c.seed, c.init);
         if (cg_mode) check_bound = 1e-10 * umax;
@@ -473,7 +571,8 @@ int main(int argc, char** argv) {
                     c.source == 1 ? "poly" : "random", amp, src_setup_ms, src_mib);
     }
     if (cg_mode) {
-      std::printf("solver    = cg\n");
+      std::printf("solver    = %s\n", cheby_mode ? "chebyshev" : "cg");
+      if (cheby_mode) std::printf("rho       = %.17g%s\n", rho_used, ho.rho == 0 ? " (closed form)" : "");
       if (cg_fixed)
         std::printf("solve     = fixed count, %s norm, check every %d iterations\n", co.norm ? "max" : "l2",
                     co.check_every);
@@ -517,9 +616,11 @@ int main(int argc, char** argv) {
     if (halo_us > 0)
       std::printf("halo      : %0.2f us per exchange (%zu B, %zu msgs per rank)\n", halo_us, hbytes, hmsgs);
     std::printf("residual  : %.10e\n", resid);
-    if (cg_mode) std::printf("true resid: %.10e (max %.10e)\n", cr.true_residual, cr.true_residual_max);
+    if (cg_mode && !cheby_mode)
+      std::printf("true resid: %.10e (max %.10e)\n", cr.true_residual, cr.true_residual_max);
     if (max_diff >= 0 && cg_mode)
-      std::printf("check     : max|diff| vs serial cg = %.3e (bound %.3e) %s\n", max_diff, check_bound,
+      std::printf("check     : max|diff| vs serial %s = %.3e (bound %.3e) %s\n", cheby_mode ? "chebyshev" : "cg",
+                  max_diff, check_bound,
                   max_diff <= check_bound ? "OK" : "FAIL");
     else if (max_diff >= 0)
       std::printf("check     : max|diff| vs serial = %.3e %s\n", max_diff, max_diff < 1e-10 ? "OK" : "FAIL");
@@ -534,9 +635,13 @@ int main(int argc, char** argv) {
       j.add("converged", sr.converged != 0).add("sweeps", sr.sweeps).add("residual_sweeps", sr.residual_sweeps)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
     if (cg_mode)
-      j.add("solver", "cg").add("converged", cr.converged != 0).add("iters", cr.iters)
+      j.add("solver", cheby_mode ? "chebyshev" : "cg").add("converged", cr.converged != 0).add("iters", cr.iters)
           .add("residual_iters", cr.residual_iters).add("checks", cr.checks).add("solve_ms", solve_ms).add("r0", cr.r0)
-          .add("residual_max", cr.residual_max).add("true_residual", cr.true_residual);
+          .add("residual_max", cr.residual_max);
+    if (cheby_mode)
+      j.add("rho", rho_used);
+    else if (cg_mode)
+      j.add("true_residual", cr.true_residual);
     if (c.source != 0)
       j.add("source", c.source == 1 ? "poly" : "random").add("src_every", src_every > 0 ? src_every : 1)
           .add("source_setup_ms", src_setup_ms);

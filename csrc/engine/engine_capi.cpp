@@ -242,6 +242,29 @@ int gmt_engine_jacobi_cg(void* p, const gmt_engine_cg_opts* o, gmt_engine_cg_res
           r.residual_max, r.r0, r.true_residual, r.true_residual_max, r.failed};
   return 0;
 }
+int gmt_engine_jacobi_cheby(void* p, const gmt_engine_cheby_opts* o, gmt_engine_cheby_result* out) {
+  if (!p || !o || !out) return 1;
+  gmt::watchdog_kick("engine: jacobi cheby");
+  auto& s = *static_cast<Handle*>(p)->s;
+  if (s.periodic()) return 2;
+  gmt::ChebyOpts co;
+  co.tol = o->tol;
+  co.rtol = o->rtol;
+  co.norm = o->norm;
+  co.max_iters = o->max_iters;
+  co.check_every = o->check_every;
+  co.lag = o->lag;
+  co.rho = o->rho;
+  gmt::ChebyResult r;
+  try {
+    r = s.cheby(co);
+  } catch (const std::invalid_argument&) {
+    return 1;
+  }
+  *out = {r.converged, r.iters, r.checks, r.residual_iters, r.residual, r.residual_max, r.r0, r.rho, r.failed};
+  return 0;
+}
+double gmt_engine_cheby_rho(int64_t nx_global, int64_t ny_global) { return gmt::cheby_rho(nx_global, ny_global); }
 int gmt_engine_jacobi_periodic(void* p) { return p && static_cast<Handle*>(p)->s->periodic() ? 1 : 0; }
 int gmt_engine_jacobi_exchange(void* p) {
   gmt::watchdog_kick("engine: halo exchange");

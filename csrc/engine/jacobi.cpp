@@ -1066,9 +1066,9 @@ void JacobiSolver::rn_setup() {
   for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
 }
 
-void JacobiSolver::enqueue_residual() {
+void JacobiSolver::enqueue_residual(bool ring_current) {
   rn_setup();
-  if (!fresh_[parity_]) exchange_now(parity_);
+  if (!ring_current && !fresh_[parity_]) exchange_now(parity_);
   GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, src_f(), src_ld(), kC0,
                                                  src_c1(), rn_dev_.data(), rn_ws_.data(), s_));
   t_.allreduce_sum(rn_dev_.data(), 1, s_);
@@ -1248,6 +1248,116 @@ CgResult JacobiSolver::cg(const CgOpts& o) {
   synchronize();
   res.true_residual = std::sqrt(rn_ring_[0]);
   res.true_residual_max = rn_ring_[1];
+  return res;
+}
+
+// ---- Chebyshev semi-iteration (gmt/jacobi.hpp ChebyOpts) ----
+
+double cheby_rho(int64_t nx_global, int64_t ny_global) {
+  const double pi = 3.14159265358979323846;
+  return 0.5 * (std::cos(pi / static_cast<double>(nx_global + 1)) + std::cos(pi / static_cast<double>(ny_global + 1)));
+}
+
+double cheby_next_weight(double rho2, double w, int k) {
+  // volatile: the product is rounded before the subtraction on any target
+  volatile double t = k == 1 ? 0.5 * rho2 : 0.25 * rho2;
+  if (k != 1) t = t * w;
+  return 1.0 / (1.0 - t);
+}
+
+void JacobiSolver::cheby_setup() {
+  if (cheby_halo_[0]) return;
+  watchdog_kick("jacobi: cheby set-up");
+  // the 1-wide ring around either buffer's interior: faces only, the
+  // plus-shaped stencil reads no corner
+  Neighbors nb = nb_;
+  nb.sw = nb.se = nb.nw = nb.ne = -2;
+  for (int b = 0; b < 2; ++b) {
+    Span2D<double> f(buf_[b].data() + (yo_ - 1) * ld_ + (xo_ - 1), nx_ + 2, ny_ + 2, ld_);
+    cheby_halo_[b] = std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, false);
+  }
+  rn_setup();
+  watchdog_kick("jacobi: cheby ready");
+}
+
+ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
+  const int every = o.check_every == 0 ? 10 : o.check_every;
+  if (every < 1 || o.max_iters < 1 || o.max_iters % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
+      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !std::isfinite(o.tol) ||
+      !std::isfinite(o.rtol) || !(o.rho == 0.0 || (std::isfinite(o.rho) && o.rho > 0.0 && o.rho < 1.0)))
+    throw std::invalid_argument("JacobiSolver::cheby: max_iters must be a positive multiple of check_every >= 1, "
+                                "0 <= lag <= 8, norm 0 or 1, tol and rtol finite and >= 0, rho 0 or in (0, 1)");
+  if (periodic())
+    throw std::invalid_argument("JacobiSolver::cheby: the spectral radius is 1 on a periodic axis");
+  cheby_setup();
+  const bool fixed = !(o.tol > 0.0) && !(o.rtol > 0.0);  // run exactly max_iters iterations
+  const int slots = o.lag + 1, last = o.max_iters / every;  // checks 0..last
+  ChebyResult res;
+  res.rho = o.rho == 0.0 ? cheby_rho(cfg_.nx_global, cfg_.ny_global) : o.rho;
+  const double rho2 = res.rho * res.rho;
+  double w = 1.0;  // the weight of the last iteration
+  int decided = 0;
+  bool stop = false;
+  bool ring = false;  // the current buffer's 1-wide faces hold the neighbours' current values
+  auto exchange = [&] {
+    if (ring || fresh_[parity_]) return;
+    Halo2D& h = *cheby_halo_[parity_];
+    if (h.active()) {
+      h.start(s_);
+      h.finish(s_);
+    }
+    ring = true;
+  };
+  auto decide = [&](int i) {
+    GMT_CHECK("cheby check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
+    watchdog_kick("jacobi cheby check");
+    const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
+    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
+    res.residual_iters = i * every;
+    res.residual = r;
+    res.residual_max = mx;
+    if (i == 0) res.r0 = r;
+    if (!std::isfinite(sum) || !std::isfinite(mx)) {
+      res.failed = 1;
+      stop = true;
+    } else if (!fixed && r <= std::max(o.tol, o.rtol * res.r0)) {
+      res.converged = 1;
+      stop = true;
+    }
+  };
+  // iteration k + 1 of this call (k = 0: the plain sweep, w_1 = 1)
+  auto iterate = [&](int k) {
+    exchange();
+    if (k == 0) {
+      sweep_full(parity_, nullptr);
+    } else {
+      w = cheby_next_weight(rho2, w, k);
+      GMT_CHECK("cheby step", gmt_cheby_step(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, src_f(), src_ld(), kC0,
+                                             src_c1(), w, buf_[parity_ ^ 1].data(), ld_, s_));
+    }
+    fresh_[parity_ ^ 1] = false;
+    parity_ ^= 1;
+    ring = false;
+  };
+  int k = 0;
+  for (int i = 0; i <= last && !stop; ++i) {
+    if (i > 0) {
+      for (int j = 0; j < every; ++j) iterate(k++);
+      res.iters += every;
+      advanced_ = true;
+      watchdog_kick("jacobi cheby iterations enqueued");
+    }
+    exchange();
+    enqueue_residual(true);
+    GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), rn_dev_.data(),
+                                               2 * sizeof(double), s_));
+    GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
+    res.checks = i + 1;
+    if (i >= o.lag) decide(decided++);
+  }
+  while (!stop && decided < res.checks) decide(decided++);
+  if (res.iters > 0) fresh_[0] = fresh_[1] = false;  // only the faces of one buffer were exchanged
+  synchronize();
   return res;
 }
 

@@ -410,6 +410,32 @@ int gmt_cg_dir(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* num
   return 0;
 }
 
+// the Chebyshev step (csrc/kernels/cheby.hip): the same checks, codes and cell
+// expression (this file is built with -ffp-contract=off)
+int gmt_cheby_step_path(int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*,
+                        int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_cheby_step(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld, const double* f,
+                   int64_t ldf, double c0, double c1, double w, double* v, int64_t ldv, void*) {
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (!u || !v || x0 < 1 || y0 < 1 || ld < x0 + nx + 1 || ldv < x0 + nx || (f && ldf < x0 + nx)) return 1;
+  for (int64_t y = y0; y < y0 + ny; ++y)
+    for (int64_t x = x0; x < x0 + nx; ++x) {
+      const double* c = u + y * ld + x;
+      double o = c0 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+      if (f) o = o + c1 * f[y * ldf + x];
+      const double pv = v[y * ldv + x];
+      const double t = o - pv;
+      const double wt = w * t;
+      v[y * ldv + x] = pv + wt;
+    }
+  return 0;
+}
+
 int gmt_jacobi5_rects(int n_rect, const int64_t* r, const double* u, double* un, int64_t ld,
                       const double* f, int64_t ldf, double c0, double c1, void*) {
   if (n_rect > 4) return 1;

@@ -101,6 +101,27 @@ typedef struct gmt_engine_cg_result {
 /* 0; 1 on invalid options, 2 on an engine with a periodic axis (nothing
  * enqueued either way).  Collective. */
 int gmt_engine_jacobi_cg(void* h, const gmt_engine_cg_opts* opts, gmt_engine_cg_result* out);
+/* Chebyshev semi-iteration from the current field (JacobiSolver::cheby,
+ * gmt/jacobi.hpp ChebyOpts / ChebyResult): cg's criterion, lagged check and
+ * fixed-count mode; one halo exchange and one kernel per iteration. */
+typedef struct gmt_engine_cheby_opts {
+  double tol, rtol;
+  int norm;        /* 0 L2, 1 max */
+  int max_iters;   /* a positive multiple of check_every */
+  int check_every; /* 0 = 10 */
+  int lag;         /* 0..8 */
+  double rho;      /* 0 = the closed form, else finite and in (0, 1) */
+} gmt_engine_cheby_opts;
+typedef struct gmt_engine_cheby_result {
+  int converged, iters, checks, residual_iters;
+  double residual, residual_max, r0, rho;
+  int failed; /* 1: a non-finite residual stopped the iteration */
+} gmt_engine_cheby_result;
+/* 0; 1 on invalid options, 2 on an engine with a periodic axis (nothing
+ * enqueued either way).  Collective. */
+int gmt_engine_jacobi_cheby(void* h, const gmt_engine_cheby_opts* opts, gmt_engine_cheby_result* out);
+/* the closed-form spectral radius of an nx x ny global interior */
+double gmt_engine_cheby_rho(int64_t nx_global, int64_t ny_global);
 /* 1 when the engine has a periodic axis */
 int gmt_engine_jacobi_periodic(void* h);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,

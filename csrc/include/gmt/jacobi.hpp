@@ -163,6 +163,43 @@ struct CgResult {
   int failed = 0;           // 1: a non-finite residual stopped the iteration
 };
 
+// JacobiSolver::cheby: Chebyshev semi-iteration over the sweep G (Golub-Varga),
+//   u_1 = G(u_0);  u_{k+1} = u_{k-1} + w_{k+1} * (G(u_k) - u_{k-1}),
+//   w_2 = 1/(1 - rho^2/2),  w_{k+1} = 1/(1 - rho^2 w_k/4),
+// rho the spectral radius of J with a zero ring on the global interior
+// (cheby_rho).  CG's order of convergence with the communication of one single
+// sweep: a 1-wide halo exchange and one kernel per iteration, no reductions.
+// The residual is not monotone from one iteration to the next; "converged"
+// means what solve() means, the first check that meets the criterion.
+struct ChebyOpts {
+  double tol = 0.0, rtol = 0.0;  // both 0: fixed-count mode, exactly max_iters iterations
+  int norm = 0;                  // 0: L2, 1: max |d|
+  int max_iters = 0;             // the cap: a positive multiple of check_every
+  int check_every = 0;           // iterations between two checks (0 = 10)
+  int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
+  // 0: the closed form.  Otherwise finite and in (0, 1): an over-estimate
+  // converges more slowly, an under-estimate can stagnate.
+  double rho = 0.0;
+};
+struct ChebyResult {
+  int converged = 0;        // the criterion was met
+  int iters = 0;            // iterations run: residual_iters + lag * check_every unless the cap came first
+  int checks = 0;           // checks enqueued
+  int residual_iters = 0;   // iteration count of the deciding check
+  double residual = 0.0;    // its residual in the chosen norm,
+  double residual_max = 0.0;  // its max |d|,
+  double r0 = 0.0;          // and the residual of the starting field (chosen norm)
+  double rho = 0.0;         // the spectral radius used
+  int failed = 0;           // 1: a non-finite residual stopped the iteration
+};
+// 0.5*(cos(pi/(nx+1)) + cos(pi/(ny+1))): the spectral radius of the Laplace
+// sweep on an nx x ny interior with a zero ring
+double cheby_rho(int64_t nx_global, int64_t ny_global);
+// w_{k+1} from w_k (k >= 1; w_1 = 1): 1/(1 - rho2/2) for k = 1, else
+// 1/(1 - rho2*w_k/4), every operation rounded once in exactly this order, so
+// the weights are bit for bit Python's given the same rho
+double cheby_next_weight(double rho2, double w, int k);
+
 class JacobiSolver {
  public:
   JacobiSolver(comm::Transport& t, const JacobiConfig& c);
@@ -202,6 +239,21 @@ class JacobiSolver {
   // std::invalid_argument on bad options or an engine with a periodic axis
   // (A is singular there); nothing is enqueued then.
   CgResult cg(const CgOpts& o);
+  // Chebyshev semi-iteration from the current field (ChebyOpts above).  One
+  // iteration is a 1-wide faces-only exchange of the current buffer's ring,
+  // one launch (the first of a call the plain sweep, later ones
+  // gmt_cheby_step with that iteration's weight by value, writing u_{k+1} over
+  // u_{k-1} in the other buffer) and the parity flip of step(), in serial
+  // order on the compute stream.  Check i is solve()'s (the read-only residual
+  // of the current field after i * check_every iterations), decided `lag`
+  // checks behind.  Every cell's arithmetic is independent of the
+  // decomposition: the field is bitwise the same on every process grid.
+  // Every call restarts the recurrence from the current field; run(k)
+  // afterwards keeps sweeping from it and captured graphs stay valid.  The
+  // first call builds two halo plans (collective).  Throws
+  // std::invalid_argument on bad options or an engine with a periodic axis
+  // (rho = 1, the fixed point is not unique); nothing is enqueued then.
+  ChebyResult cheby(const ChebyOpts& o);
   // one blocking halo exchange of the current field (latency measurements);
   // ordered after every pass already enqueued
   void exchange_only();
@@ -303,10 +355,13 @@ class JacobiSolver {
   int halo_mask() const;
   void split_cus();
   void setup_push();
-  void enqueue_residual();  // {sum d^2, max |d|} over every rank into rn_dev_, stream-ordered on s_
+  // {sum d^2, max |d|} over every rank into rn_dev_, stream-ordered on s_;
+  // ring_current: the 1-wide faces of the current buffer were just exchanged
+  void enqueue_residual(bool ring_current = false);
   void rn_setup();          // rn_ws_, rn_dev_, the ring and its events (first use)
   void cg_setup();          // the state of cg() (first use; collective)
   void cg_reduce(double* pair);  // all-reduce {sum, max} so every rank holds the same bits
+  void cheby_setup();       // the halo plans of cheby() (first use; collective)
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
   void push_pass(int parity, int k);   // the pass launch alone
@@ -352,6 +407,8 @@ class JacobiSolver {
   // rr by iteration parity at [0..1] and [2..3], p.q at [4..5]
   Buffer<double> cg_r_, cg_p_, cg_q_, cg_ws_, cg_sc_;
   std::unique_ptr<Halo2D> cg_halo_;
+  // cheby(): the 1-wide ring of either buffer's interior (faces only)
+  std::unique_ptr<Halo2D> cheby_halo_[2];
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values
   gmt_stream_t s_ = nullptr, cs_ = nullptr;

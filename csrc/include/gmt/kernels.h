@@ -262,6 +262,30 @@ int gmt_cg_update_path(int64_t x0, const double* p, int64_t ldp, const double* q
                        int64_t ldx, const double* r, int64_t ldr);
 int gmt_cg_dir_path(int64_t x0, const double* r, int64_t ldr, const double* p, int64_t ldp);
 
+/* ---- Chebyshev semi-iteration over the Laplace sweep (csrc/kernels/cheby.hip):
+ *      the one launch of an iteration of JacobiSolver::cheby,
+ *        v' = v + w*(G(u) - v),  G(u) = c0*((W+E)+(S+N)) [+ c1*f],
+ *      u the current iterate, v the previous one, overwritten in place by the
+ *      next; w by value.  Conventions of gmt_cg_apply: absolute x0 >= 1, nx,
+ *      y0 >= 1, ny, ld >= x0 + nx + 1, ldv and ldf >= x0 + nx, asynchronous on
+ *      `stream`.  The cell is evaluated without contraction on both backends,
+ *      in the order o = c0*((w+e)+(n+s)); o = o + c1*f (only with f);
+ *      t = o - v; v' = v + (w*t), so v' is bitwise NumPy's.  f may be NULL.
+ *      u and v must not overlap: v' of one cell would be another cell's
+ *      neighbour.  No cell outside the region is written; u is read only on
+ *      the region's plus-shaped set, v and f only on the region.  An empty
+ *      region (nx or ny 0) launches nothing and returns 0.  Refused (non-zero,
+ *      the same on both backends): a NULL u or v, a negative extent, x0 < 1 or
+ *      y0 < 1, a short pitch.  24 B per point, 32 with f. */
+int gmt_cheby_step(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld, const double* f,
+                   int64_t ldf, double c0, double c1, double w, double* v, int64_t ldv, void* stream);
+/* The kernel the call would launch, nothing launched: GMT_PATH_ROW_WALK (x0
+ * even, every pointer 16-B aligned, every pitch even; *seg_rows, may be NULL,
+ * = rows per segment) or GMT_PATH_SCALAR (*seg_rows = 0); f counts only when
+ * non-NULL.  GMT_PATH_NONE on the CPU backend. */
+int gmt_cheby_step_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f,
+                        int64_t ldf, const double* v, int64_t ldv, int64_t* seg_rows);
+
 /* ---- Temporal-blocking Jacobi (csrc/kernels/jacobi5tb.hip): `sweeps` fused
  *      Laplace sweeps per memory pass, un = J^sweeps(u), on up to 8 output
  *      rects {x0, nx, y0, ny} (absolute array coordinates, x0 >= sweeps,

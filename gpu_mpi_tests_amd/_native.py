@@ -168,6 +168,11 @@ _SIGS = {
     "gmt_cg_apply_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_cg_update_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
     "gmt_cg_dir_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "gmt_cheby_step": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
+    ),
+    "gmt_cheby_step_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_jacobi5_rects": (
         c_int,
         [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp],

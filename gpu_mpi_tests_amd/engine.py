@@ -82,6 +82,21 @@ class CgResult(ctypes.Structure):
                 ("true_residual_max", ctypes.c_double), ("failed", ctypes.c_int)]
 
 
+class ChebyOpts(ctypes.Structure):
+    """gmt_engine_cheby_opts (csrc/include/gmt/engine.h)."""
+    _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
+                ("max_iters", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
+                ("rho", ctypes.c_double)]
+
+
+class ChebyResult(ctypes.Structure):
+    """gmt_engine_cheby_result (csrc/include/gmt/engine.h)."""
+    _fields_ = [("converged", ctypes.c_int), ("iters", ctypes.c_int), ("checks", ctypes.c_int),
+                ("residual_iters", ctypes.c_int), ("residual", ctypes.c_double),
+                ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("rho", ctypes.c_double),
+                ("failed", ctypes.c_int)]
+
+
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
 CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
@@ -136,6 +151,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_solve.restype = c_int
     lib.gmt_engine_jacobi_cg.argtypes = [vp, ctypes.POINTER(CgOpts), ctypes.POINTER(CgResult)]
     lib.gmt_engine_jacobi_cg.restype = c_int
+    lib.gmt_engine_jacobi_cheby.argtypes = [vp, ctypes.POINTER(ChebyOpts), ctypes.POINTER(ChebyResult)]
+    lib.gmt_engine_jacobi_cheby.restype = c_int
     lib.gmt_engine_jacobi_periodic.argtypes = [vp]
     lib.gmt_engine_jacobi_periodic.restype = c_int
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
@@ -603,6 +620,51 @@ class NativeJacobi:
             raise ValueError("gmt_engine_jacobi_cg rejected its options")
         return {n: getattr(r, n) for n, _ in CgResult._fields_}
 
+    def cheby(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_iters: int = 0,
+              check_every: int = 0, lag: int = 1, rho: float = 0.0) -> dict:
+        """Chebyshev semi-iteration over the sweep from the current field
+        (JacobiSolver::cheby): ``u_1 = G(u_0)``,
+        ``u_{k+1} = u_{k-1} + w_{k+1} (G(u_k) - u_{k-1})`` with the weights of
+        :func:`cheby_weights`, until the residual of :meth:`residual_norm` meets
+        ``r <= max(tol, rtol * r0)`` at a check or ``max_iters`` iterations have
+        run.  CG's order of convergence at the communication of single sweeps:
+        one 1-wide halo exchange and one kernel per iteration, no reductions
+        between checks; the field is bitwise the same on every process grid.
+        Options as :meth:`cg` (``tol == rtol == 0``: exactly ``max_iters``
+        iterations).  ``rho``: the spectral radius of the sweep, 0 = the closed
+        form :func:`cheby_rho` of the global interior; a supplied value must be
+        finite and in (0, 1) — an over-estimate converges more slowly, an
+        under-estimate can stagnate.  The residual is not monotone from one
+        iteration to the next: "converged" is the first *check* that meets the
+        criterion.  Every call restarts the recurrence from the current field;
+        :meth:`run` afterwards keeps sweeping from it.  Returns the fields of
+        ChebyResult: ``converged``, ``iters``, ``checks``, ``residual_iters``,
+        ``residual``, ``residual_max``, ``r0``, ``rho`` (the value used),
+        ``failed``.  Identical on every rank.  Dirichlet engines only.
+        Collective."""
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
+        every = int(check_every) if check_every else CG_CHECK_EVERY
+        if isinstance(lag, bool) or not 0 <= int(lag) <= MAX_LAG:
+            raise ValueError(f"lag must be 0..{MAX_LAG}, got {lag!r}")
+        if every < 1:
+            raise ValueError(f"check_every must be >= 1 (0 = {CG_CHECK_EVERY}), got {check_every!r}")
+        if int(max_iters) < 1 or int(max_iters) % every:
+            raise ValueError(f"max_iters must be a positive multiple of check_every ({every}), got {max_iters!r}")
+        tol, rtol, rho = float(tol), float(rtol), float(rho)
+        if not (np.isfinite(tol) and np.isfinite(rtol)) or tol < 0 or rtol < 0:
+            raise ValueError("tol and rtol must be finite and >= 0")
+        if rho != 0.0 and not (np.isfinite(rho) and 0.0 < rho < 1.0):
+            raise ValueError(f"rho must be 0 (the closed form) or finite and in (0, 1), got {rho!r}")
+        if self.lib.gmt_engine_jacobi_periodic(self.h):
+            raise ValueError("cheby needs Dirichlet sides: the spectral radius is 1 on a periodic axis")
+        o = ChebyOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_iters=int(max_iters), check_every=every,
+                      lag=int(lag), rho=rho)
+        r = ChebyResult()
+        if self.lib.gmt_engine_jacobi_cheby(self.h, ctypes.byref(o), ctypes.byref(r)):
+            raise ValueError("gmt_engine_jacobi_cheby rejected its options")
+        return {n: getattr(r, n) for n, _ in ChebyResult._fields_}
+
     def interior(self) -> np.ndarray:
         out = np.empty((self.ny, self.nx), dtype=np.float64)
         self.lib.gmt_engine_jacobi_copy_interior(self.h, out.ctypes.data)
@@ -851,3 +913,69 @@ def serial_cg(ny: int, nx: int, iters: int, init: str = "analytic", seed: int = 
         if keep is not None and it + 1 in keep:
             kept[it + 1] = c.copy()
     return (c.copy() if keep is None else kept), series
+
+
+def cheby_rho(ny: int, nx: int) -> float:
+    """The spectral radius of the Laplace sweep on an ny x nx interior with a
+    zero ring: ``0.5*(cos(pi/(nx+1)) + cos(pi/(ny+1)))``, the default ``rho`` of
+    :meth:`NativeJacobi.cheby` (whose result reports the value it used: the two
+    ``cos`` may differ by an ulp)."""
+    return 0.5 * (math.cos(math.pi / (nx + 1)) + math.cos(math.pi / (ny + 1)))
+
+
+def cheby_weights(rho: float, n: int) -> list:
+    """``[w_1, ..., w_n]`` of :meth:`NativeJacobi.cheby`: ``w_1 = 1``,
+    ``w_2 = 1/(1 - rho^2/2)``, ``w_{k+1} = 1/(1 - rho^2 w_k/4)``, in the
+    engine's expression order (bit for bit its weights given the same rho)."""
+    rho2 = rho * rho
+    w = []
+    for k in range(n):
+        w.append(1.0 if k == 0 else 1.0 / (1.0 - 0.5 * rho2) if k == 1 else 1.0 / (1.0 - 0.25 * rho2 * w[-1]))
+    return w
+
+
+def serial_cheby(ny: int, nx: int, iters: int, rho: float, init: str = "analytic", seed: int = 0,
+                 source: "str | np.ndarray | None" = None, source_amp: float = 1.0, restart_every=None,
+                 keep=None, resid_every=None):
+    """NumPy definition of :meth:`NativeJacobi.cheby` on the whole Dirichlet
+    problem: ``iters`` Chebyshev iterations from the engine's initial field with
+    the weights of :func:`cheby_weights` for ``rho``, every cell in the kernel's
+    operation order (``o = 0.25*((w+e)+(n+s))``, ``o = o + 1.0*f``,
+    ``t = o - v``, ``v + w*t``) — bitwise the engine's field.
+    ``restart_every``: the recurrence restarts (``w_1 = 1``) every that many
+    iterations, as a further ``cheby()`` call does.  Returns
+    ``(field, series)``: the ny x nx interior after the last iteration — or,
+    with ``keep`` (iteration counts), the dict ``{k: interior after k}`` — and,
+    with ``resid_every``, the dict ``{k: (L2, max)}`` of the residual
+    ``G(u) - u`` by ``math.fsum`` after every k that is a multiple of it
+    (0 included)."""
+    u = initial_field(ny, nx, init, seed)
+    v = u.copy()
+    s = None if source is None else source_field(ny, nx, source, seed, source_amp)
+    period = int(restart_every) if restart_every else max(int(iters), 1)
+    weights = cheby_weights(rho, min(period, max(int(iters), 1)))
+
+    def sweep(a):
+        o = 0.25 * ((a[1:-1, :-2] + a[1:-1, 2:]) + (a[:-2, 1:-1] + a[2:, 1:-1]))
+        return o if s is None else o + 1.0 * s
+
+    def resid(a):
+        d = sweep(a) - a[1:-1, 1:-1]
+        return math.sqrt(math.fsum((d * d).ravel().tolist())), float(np.abs(d).max())
+
+    kept = {0: u[1:-1, 1:-1].copy()} if keep is not None and 0 in keep else {}
+    series = {0: resid(u)} if resid_every else {}
+    for it in range(iters):
+        k = it % period
+        if k == 0:
+            v[1:-1, 1:-1] = sweep(u)
+        else:
+            pv = v[1:-1, 1:-1]
+            t = sweep(u) - pv
+            v[1:-1, 1:-1] = pv + weights[k] * t
+        u, v = v, u
+        if keep is not None and it + 1 in keep:
+            kept[it + 1] = u[1:-1, 1:-1].copy()
+        if resid_every and (it + 1) % resid_every == 0:
+            series[it + 1] = resid(u)
+    return (u[1:-1, 1:-1].copy() if keep is None else kept), series

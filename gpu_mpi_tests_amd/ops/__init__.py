@@ -6,7 +6,7 @@ K4/K5/K11 ``stencil5_2d`` (and its ``stencil5_2d_edges`` /
 K9 ``sum_axis``; K10/K12 ``diff_sq``/``diff_norm``; analytic ``fill_poly``;
 and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
 its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
-``cg_apply`` / ``cg_update`` / ``cg_dir``
+``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``
 and ``jacobi5tb`` (K fused sweeps per memory pass).
 """
 from .kernels import (  # noqa: F401
@@ -19,6 +19,8 @@ from .kernels import (  # noqa: F401
     cg_dir_path,
     cg_update,
     cg_update_path,
+    cheby_step,
+    cheby_step_path,
     copy2d_batched,
     daxpy,
     diff_norm,

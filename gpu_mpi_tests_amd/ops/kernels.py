@@ -532,6 +532,49 @@ def cg_dir_path(r: torch.Tensor, p: torch.Tensor, region: tuple[int, int, int, i
     return int(_native.lib().gmt_cg_dir_path(int(region[0]), r.data_ptr(), r.stride(0), p.data_ptr(), p.stride(0)))
 
 
+def _storage_span(t: torch.Tensor) -> tuple[int, int]:
+    """[first byte, one past the last byte) a 2-D view can touch."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = (t.shape[0] - 1) * t.stride(0) + (t.shape[1] - 1) * t.stride(1)
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def cheby_step(u: torch.Tensor, v: torch.Tensor, w: float, region: tuple[int, int, int, int],
+               f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 1.0) -> torch.Tensor:
+    """One Chebyshev semi-iteration over ``region = (x0, nx, y0, ny)``
+    (gmt_cheby_step): ``v <- v + w*(G(u) - v)`` with
+    ``G(u) = c0*((W + E) + (S + N)) [+ c1*f]``; ``u`` is the current iterate,
+    ``v`` the previous one, overwritten by the next.  No contraction: ``v`` is
+    bitwise NumPy's (:func:`reference.cheby_step`).  ``u`` and ``v`` must not
+    share storage.  Returns ``v``."""
+    _check2d(u, "cheby_step.u")
+    _check2d(v, "cheby_step.v")
+    if f is not None:
+        _check2d(f, "cheby_step.f")
+    (ua, ub), (va, vb) = _storage_span(u), _storage_span(v)
+    if ua < vb and va < ub:
+        raise ValueError("cheby_step: u and v must not share storage")
+    x0, nx, y0, ny = (int(t) for t in region)
+    if not _is_dev(v):
+        return ref.cheby_step(u, v, w, x0, nx, y0, ny, f, c0, c1)
+    _native.check(_native.lib().gmt_cheby_step(x0, nx, y0, ny, u.data_ptr(), u.stride(0), *_ptr_ld(f), float(c0),
+                                               float(c1), float(w), v.data_ptr(), v.stride(0), _stream(v)),
+                  "gmt_cheby_step")
+    return v
+
+
+def cheby_step_path(u: torch.Tensor, v: torch.Tensor, region: tuple[int, int, int, int],
+                    f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`cheby_step` would launch (gmt_cheby_step_path, no
+    launch): ``(PATH_ROW_WALK or PATH_SCALAR, rows per segment of the row walk)``."""
+    x0, nx, _, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_cheby_step_path(x0, nx, ny, u.data_ptr(), u.stride(0), *_ptr_ld(f), v.data_ptr(),
+                                             v.stride(0), ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
 def jacobi5_rects(u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],
                   f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> None:
     """Sweep up to 4 rectangles (the boundary frame of an overlapped step) in one launch."""

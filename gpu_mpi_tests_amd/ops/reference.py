@@ -155,6 +155,23 @@ def cg_dir(num, den, r, p, x0: int, nx: int, y0: int, ny: int) -> torch.Tensor:
     return p
 
 
+def cheby_step(u: torch.Tensor, v: torch.Tensor, w: float, x0: int, nx: int, y0: int, ny: int,
+               f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 1.0) -> torch.Tensor:
+    """gmt_cheby_step: v <- v + w*(G(u) - v) over the region, every operation rounded once."""
+    if nx < 0 or ny < 0:
+        raise ValueError("cheby_step: negative extent")
+    if nx > 0 and ny > 0:
+        ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+        o = c0 * ((u[ys, x0 - 1 : x0 - 1 + nx] + u[ys, x0 + 1 : x0 + 1 + nx])
+                  + (u[y0 - 1 : y0 - 1 + ny, xs] + u[y0 + 1 : y0 + 1 + ny, xs]))
+        if f is not None:
+            o = o + c1 * f[ys, xs]
+        pv = v[ys, xs]
+        t = o - pv
+        v[ys, xs] = pv + w * t
+    return v
+
+
 def jacobi5xk(k: int, u: torch.Tensor, un: torch.Tensor, rects, dom, halo_mask: int = 0) -> None:
     """fp64 reference of k fused Laplace sweeps with the ghost-side rule of
     csrc/kernels/jacobi5tb.hip: a ring cell outside ``dom`` gets an
