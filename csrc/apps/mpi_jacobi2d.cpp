@@ -433,14 +433,7 @@ int main(int argc, char** argv) {
       t_step = dt / (hr.iters > 0 ? hr.iters : 1);
       total_sweeps = hr.iters;
       rho_used = hr.rho;
-      cr.converged = hr.converged;
-      cr.iters = hr.iters;
-      cr.checks = hr.checks;
-      cr.residual_iters = hr.residual_iters;
-      cr.residual = hr.residual;
-      cr.residual_max = hr.residual_max;
-      cr.r0 = hr.r0;
-      cr.failed = hr.failed;
+      static_cast<CheckResult&>(cr) = hr;  // reported through --cg's lines
     } else if (cg_mode) {
       // the warm-up runs one check's worth of iterations (first launches, the
       // state of cg()), then the field is the initial one again
@@ -471,8 +464,8 @@ int main(int argc, char** argv) {
       double dt = wtime() - t0;
       MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
       solve_ms = dt * 1e3;
-      t_step = dt / (sr.sweeps > 0 ? sr.sweeps : 1);
-      total_sweeps = sr.sweeps;
+      t_step = dt / (sr.iters > 0 ? sr.iters : 1);
+      total_sweeps = sr.iters;
     } else {
       solver.run(n_warmup);
       solver.synchronize();
@@ -602,7 +595,7 @@ int main(int argc, char** argv) {
       else
         std::printf("steps     = at most %d\n", so.max_sweeps);
       std::printf("converged : %s%s\n", sr.converged ? "yes" : "no", sr.failed ? " (non-finite residual)" : "");
-      std::printf("sweeps    : %d (criterion met at %d, %d checks, lag %d)\n", sr.sweeps, sr.residual_sweeps, sr.checks,
+      std::printf("sweeps    : %d (criterion met at %d, %d checks, lag %d)\n", sr.iters, sr.residual_iters, sr.checks,
                   so.lag);
       std::printf("TIME solve: %0.6f ms\n", solve_ms);
     } else {
@@ -632,7 +625,7 @@ int main(int argc, char** argv) {
         .add("MLUPS", mlups).add("halo_us", halo_us).add("halo_bytes", hbytes).add("residual", resid)
         .add("check_max_diff", max_diff);
     if (solve_mode)
-      j.add("converged", sr.converged != 0).add("sweeps", sr.sweeps).add("residual_sweeps", sr.residual_sweeps)
+      j.add("converged", sr.converged != 0).add("sweeps", sr.iters).add("residual_sweeps", sr.residual_iters)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
     if (cg_mode)
       j.add("solver", cheby_mode ? "chebyshev" : "cg").add("converged", cr.converged != 0).add("iters", cr.iters)

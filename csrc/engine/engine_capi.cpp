@@ -217,7 +217,7 @@ int gmt_engine_jacobi_solve(void* p, const gmt_engine_solve_opts* o, gmt_engine_
   } catch (const std::invalid_argument&) {
     return 1;
   }
-  *out = {r.converged, r.sweeps, r.checks, r.residual_sweeps, r.residual, r.residual_max, r.r0, r.failed};
+  *out = {r.converged, r.iters, r.checks, r.residual_iters, r.residual, r.residual_max, r.r0, r.failed};
   return 0;
 }
 int gmt_engine_jacobi_cg(void* p, const gmt_engine_cg_opts* o, gmt_engine_cg_result* out) {

@@ -1055,9 +1055,7 @@ double JacobiSolver::residual() {
 }
 
 // The read-only residual of the current field, all-reduced, left in rn_dev_:
-// everything stream-ordered on s_, nothing waits.  The sum is followed by a
-// max over both values: whatever order a transport adds in, every rank then
-// holds the same two doubles and takes the same decision.
+// everything stream-ordered on s_, nothing waits.
 void JacobiSolver::rn_setup() {
   if (rn_dev_.data()) return;
   rn_ws_ = Buffer<double>(static_cast<size_t>(gmt_jacobi5_resid_workspace(nx_, ny_)), GMT_SPACE_DEVICE);
@@ -1066,13 +1064,20 @@ void JacobiSolver::rn_setup() {
   for (auto& e : rn_ev_) GMT_CHECK("event", gmt_rt_event_create(&e, 0));
 }
 
+// The sum of pair[0], then a max over both values: whatever order a transport
+// adds in, every rank then holds the same two doubles and takes the same
+// decision.
+void JacobiSolver::allreduce_sum_max(double* pair) {
+  t_.allreduce_sum(pair, 1, s_);
+  t_.allreduce_max(pair, 2, s_);
+}
+
 void JacobiSolver::enqueue_residual(bool ring_current) {
   rn_setup();
   if (!ring_current && !fresh_[parity_]) exchange_now(parity_);
   GMT_CHECK("jacobi residual", gmt_jacobi5_resid(xo_, nx_, yo_, ny_, buf_[parity_].data(), ld_, src_f(), src_ld(), kC0,
                                                  src_c1(), rn_dev_.data(), rn_ws_.data(), s_));
-  t_.allreduce_sum(rn_dev_.data(), 1, s_);
-  t_.allreduce_max(rn_dev_.data(), 2, s_);
+  allreduce_sum_max(rn_dev_.data());
 }
 
 void JacobiSolver::residual_norm(double out[2]) {
@@ -1083,51 +1088,92 @@ void JacobiSolver::residual_norm(double out[2]) {
   out[1] = rn_ring_[1];
 }
 
-SolveResult JacobiSolver::solve(const SolveOpts& o) {
-  const int every = o.check_every == 0 ? ks_ : o.check_every;
-  if (every < 1 || o.max_sweeps < 1 || o.max_sweeps % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
-      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !(o.tol > 0.0 || o.rtol > 0.0) ||
-      !std::isfinite(o.tol) || !std::isfinite(o.rtol))
-    throw std::invalid_argument("JacobiSolver::solve: max_sweeps must be a positive multiple of check_every >= 1, "
-                                "0 <= lag <= 8, norm 0 or 1, and tol or rtol positive");
-  const int slots = o.lag + 1, last = o.max_sweeps / every;  // checks 0..last
-  SolveResult res;
+// The 1-wide ring around the interior of a field in the engine's layout:
+// faces only, the plus-shaped stencil reads no corner.
+std::unique_ptr<Halo2D> JacobiSolver::faces_halo(double* field) {
+  Neighbors nb = nb_;
+  nb.sw = nb.se = nb.nw = nb.ne = -2;
+  Span2D<double> f(field + (yo_ - 1) * ld_ + (xo_ - 1), nx_ + 2, ny_ + 2, ld_);
+  return std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, false);
+}
+
+// ---- the lagged check loop of solve(), cg() and cheby() ----
+
+// What the three share of their options, and the names their texts use.
+struct JacobiSolver::CheckLoop {
+  const char* method;    // "solve", "cg", "cheby"
+  const char* cap_name;  // the option `cap` is
+  const char* phase;     // the watchdog phase of a decided check
+  double tol, rtol;
+  int norm, cap, every, lag;
+  bool need_tol;         // solve(): tol or rtol must be positive (the others then run exactly `cap` iterations)
+  // extra_ok: the method's own options hold; extra_rule: how the message words them
+  void validate(bool extra_ok = true, const char* extra_rule = "") const {
+    const bool tol_ok = tol >= 0.0 && rtol >= 0.0 && std::isfinite(tol) && std::isfinite(rtol) &&
+                        (!need_tol || tol > 0.0 || rtol > 0.0);
+    if (every < 1 || cap < 1 || cap % every != 0 || lag < 0 || lag > kMaxLag || (norm != 0 && norm != 1) || !tol_ok ||
+        !extra_ok)
+      throw std::invalid_argument(std::string("JacobiSolver::") + method + ": " + cap_name +
+                                  " must be a positive multiple of check_every >= 1, 0 <= lag <= 8, norm 0 or 1, " +
+                                  (need_tol ? "and tol or rtol positive" : "tol and rtol finite and >= 0") + extra_rule);
+  }
+};
+
+// check(i) enqueues check i (after i * every iterations) and names the device
+// pair {sum, max} it leaves, all-reduced; the pair is copied into slot
+// i % (lag + 1) of the page-locked ring and decided `lag` checks later, when
+// the host waits for its event only.  advance() enqueues `every` iterations.
+void JacobiSolver::run_checks(const CheckLoop& c, CheckResult& res, const std::function<void()>& advance,
+                              const std::function<const double*(int)>& check) {
+  const int slots = c.lag + 1, last = c.cap / c.every;   // checks 0..last
+  const bool fixed = !(c.tol > 0.0) && !(c.rtol > 0.0);  // run exactly `cap` iterations
   int decided = 0;  // checks decided so far
   bool stop = false;
   // decide on check i (its event has been recorded): every rank reads the
   // same all-reduced pair, so every rank stops at the same check
   auto decide = [&](int i) {
-    GMT_CHECK("solve check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
-    watchdog_kick("jacobi solve check");
+    GMT_CHECK(c.phase, gmt_rt_event_synchronize(rn_ev_[i % slots]));
+    watchdog_kick(c.phase);
     const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
-    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
-    res.residual_sweeps = i * every;
+    const double r = c.norm == 0 ? std::sqrt(sum) : mx;
+    res.residual_iters = i * c.every;
     res.residual = r;
     res.residual_max = mx;
     if (i == 0) res.r0 = r;
     if (!std::isfinite(sum) || !std::isfinite(mx)) {
       res.failed = 1;
       stop = true;
-    } else if (r <= std::max(o.tol, o.rtol * res.r0)) {
+    } else if (!fixed && r <= std::max(c.tol, c.rtol * res.r0)) {
       res.converged = 1;
       stop = true;
     }
   };
   for (int i = 0; i <= last && !stop; ++i) {
     if (i > 0) {
-      run(every);
-      res.sweeps += every;
+      advance();
+      res.iters += c.every;
     }
-    enqueue_residual();
-    GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), rn_dev_.data(),
-                                               2 * sizeof(double), s_));
+    const double* pair = check(i);
+    GMT_CHECK("check D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), pair, 2 * sizeof(double), s_));
     GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
     res.checks = i + 1;
-    if (i >= o.lag) decide(decided++);
+    if (i >= c.lag) decide(decided++);
   }
   // drain the outstanding checks in order (the cap, or a stop with lag > 0:
-  // the later checks' sweeps have run, an earlier check still decides)
+  // the later checks' iterations have run, an earlier check still decides)
   while (!stop && decided < res.checks) decide(decided++);
+}
+
+SolveResult JacobiSolver::solve(const SolveOpts& o) {
+  const CheckLoop loop{"solve", "max_sweeps", "jacobi solve check", o.tol, o.rtol, o.norm, o.max_sweeps,
+                       o.check_every == 0 ? ks_ : o.check_every, o.lag, true};
+  loop.validate();
+  SolveResult res;
+  run_checks(loop, res, [&] { run(loop.every); },
+             [&](int) {
+               enqueue_residual();
+               return rn_dev_.data();
+             });
   synchronize();
   return res;
 }
@@ -1147,57 +1193,21 @@ void JacobiSolver::cg_setup() {
   cg_sc_ = Buffer<double>(6, GMT_SPACE_DEVICE);
   GMT_CHECK("memset", gmt_rt_memset_async(cg_sc_.data(), 0, cg_sc_.bytes(), s_));
   GMT_CHECK("cg set-up sync", gmt_rt_stream_synchronize(s_));
-  // the 1-wide ring of p around the interior: faces only, the plus-shaped
-  // stencil reads no corner
-  Neighbors nb = nb_;
-  nb.sw = nb.se = nb.nw = nb.ne = -2;
-  Span2D<double> f(cg_p_.data() + (yo_ - 1) * ld_ + (xo_ - 1), nx_ + 2, ny_ + 2, ld_);
-  cg_halo_ = std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, false);
+  cg_halo_ = faces_halo(cg_p_.data());
   rn_setup();
   watchdog_kick("jacobi: cg ready");
 }
 
-// sum of [0], then max over both: whatever order a transport adds in, every
-// rank then holds the same two doubles (enqueue_residual's treatment)
-void JacobiSolver::cg_reduce(double* pair) {
-  t_.allreduce_sum(pair, 1, s_);
-  t_.allreduce_max(pair, 2, s_);
-}
-
 CgResult JacobiSolver::cg(const CgOpts& o) {
-  const int every = o.check_every == 0 ? 10 : o.check_every;
-  if (every < 1 || o.max_iters < 1 || o.max_iters % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
-      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !std::isfinite(o.tol) ||
-      !std::isfinite(o.rtol))
-    throw std::invalid_argument("JacobiSolver::cg: max_iters must be a positive multiple of check_every >= 1, "
-                                "0 <= lag <= 8, norm 0 or 1, tol and rtol finite and >= 0");
+  const CheckLoop loop{"cg", "max_iters", "jacobi cg check", o.tol, o.rtol, o.norm, o.max_iters,
+                       o.check_every == 0 ? 10 : o.check_every, o.lag, false};
+  loop.validate();
   if (periodic())
     throw std::invalid_argument("JacobiSolver::cg: I - J is singular on a periodic axis");
   cg_setup();
-  const bool fixed = !(o.tol > 0.0) && !(o.rtol > 0.0);  // run exactly max_iters iterations
-  const int slots = o.lag + 1, last = o.max_iters / every;  // checks 0..last
   double* u = buf_[parity_].data();
   double* sc = cg_sc_.data();
   CgResult res;
-  int decided = 0;
-  bool stop = false;
-  auto decide = [&](int i) {
-    GMT_CHECK("cg check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
-    watchdog_kick("jacobi cg check");
-    const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
-    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
-    res.residual_iters = i * every;
-    res.residual = r;
-    res.residual_max = mx;
-    if (i == 0) res.r0 = r;
-    if (!std::isfinite(sum) || !std::isfinite(mx)) {
-      res.failed = 1;
-      stop = true;
-    } else if (!fixed && r <= std::max(o.tol, o.rtol * res.r0)) {
-      res.converged = 1;
-      stop = true;
-    }
-  };
   // iteration k reads rr from parity k & 1 and leaves rr' in the other slot
   auto iterate = [&](int k) {
     double* rr = sc + 2 * (k & 1);
@@ -1209,35 +1219,31 @@ CgResult JacobiSolver::cg(const CgOpts& o) {
     }
     GMT_CHECK("cg apply", gmt_cg_apply(0, xo_, nx_, yo_, ny_, cg_p_.data(), ld_, nullptr, 0, kC0, 0.0, cg_q_.data(),
                                        ld_, pq, cg_ws_.data(), s_));
-    cg_reduce(pq);
+    allreduce_sum_max(pq);
     GMT_CHECK("cg update", gmt_cg_update(xo_, nx_, yo_, ny_, rr, pq, cg_p_.data(), ld_, cg_q_.data(), ld_, u, ld_,
                                          cg_r_.data(), ld_, rn, cg_ws_.data(), s_));
-    cg_reduce(rn);
+    allreduce_sum_max(rn);
     GMT_CHECK("cg direction", gmt_cg_dir(xo_, nx_, yo_, ny_, rn, rr, cg_r_.data(), ld_, cg_p_.data(), ld_, s_));
   };
   int k = 0;
-  for (int i = 0; i <= last && !stop; ++i) {
-    if (i == 0) {
-      // r = b - A u = the residual d of the current field; p = r on the interior
-      if (!fresh_[parity_]) exchange_now(parity_);
-      GMT_CHECK("cg residual", gmt_cg_apply(1, xo_, nx_, yo_, ny_, u, ld_, src_f(), src_ld(), kC0, src_c1(),
-                                            cg_r_.data(), ld_, sc, cg_ws_.data(), s_));
-      cg_reduce(sc);
-      const int64_t off = xo_ + yo_ * ld_;
-      const gmt_copy2d_desc d = {cg_r_.data() + off, cg_p_.data() + off, ld_, ld_, nx_, ny_};
-      GMT_CHECK("cg p = r", gmt_copy2d_batched(1, &d, sizeof(double), s_));
-    } else {
-      for (int j = 0; j < every; ++j) iterate(k++);
-      res.iters += every;
-      watchdog_kick("jacobi cg iterations enqueued");
-    }
-    GMT_CHECK("cg D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), sc + 2 * (k & 1), 2 * sizeof(double),
-                                            s_));
-    GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
-    res.checks = i + 1;
-    if (i >= o.lag) decide(decided++);
-  }
-  while (!stop && decided < res.checks) decide(decided++);
+  run_checks(loop, res,
+             [&] {
+               for (int j = 0; j < loop.every; ++j) iterate(k++);
+               watchdog_kick("jacobi cg iterations enqueued");
+             },
+             [&](int i) {
+               if (i == 0) {
+                 // r = b - A u = the residual d of the current field; p = r on the interior
+                 if (!fresh_[parity_]) exchange_now(parity_);
+                 GMT_CHECK("cg residual", gmt_cg_apply(1, xo_, nx_, yo_, ny_, u, ld_, src_f(), src_ld(), kC0, src_c1(),
+                                                       cg_r_.data(), ld_, sc, cg_ws_.data(), s_));
+                 allreduce_sum_max(sc);
+                 const int64_t off = xo_ + yo_ * ld_;
+                 const gmt_copy2d_desc d = {cg_r_.data() + off, cg_p_.data() + off, ld_, ld_, nx_, ny_};
+                 GMT_CHECK("cg p = r", gmt_copy2d_batched(1, &d, sizeof(double), s_));
+               }
+               return sc + 2 * (k & 1);  // the recursive rr of iteration k
+             });
   if (res.iters > 0) {
     fresh_[parity_] = false;  // the ghost ring was not updated
     advanced_ = true;
@@ -1268,36 +1274,22 @@ double cheby_next_weight(double rho2, double w, int k) {
 void JacobiSolver::cheby_setup() {
   if (cheby_halo_[0]) return;
   watchdog_kick("jacobi: cheby set-up");
-  // the 1-wide ring around either buffer's interior: faces only, the
-  // plus-shaped stencil reads no corner
-  Neighbors nb = nb_;
-  nb.sw = nb.se = nb.nw = nb.ne = -2;
-  for (int b = 0; b < 2; ++b) {
-    Span2D<double> f(buf_[b].data() + (yo_ - 1) * ld_ + (xo_ - 1), nx_ + 2, ny_ + 2, ld_);
-    cheby_halo_[b] = std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, false);
-  }
+  for (int b = 0; b < 2; ++b) cheby_halo_[b] = faces_halo(buf_[b].data());
   rn_setup();
   watchdog_kick("jacobi: cheby ready");
 }
 
 ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
-  const int every = o.check_every == 0 ? 10 : o.check_every;
-  if (every < 1 || o.max_iters < 1 || o.max_iters % every != 0 || o.lag < 0 || o.lag > kMaxLag ||
-      (o.norm != 0 && o.norm != 1) || !(o.tol >= 0.0) || !(o.rtol >= 0.0) || !std::isfinite(o.tol) ||
-      !std::isfinite(o.rtol) || !(o.rho == 0.0 || (std::isfinite(o.rho) && o.rho > 0.0 && o.rho < 1.0)))
-    throw std::invalid_argument("JacobiSolver::cheby: max_iters must be a positive multiple of check_every >= 1, "
-                                "0 <= lag <= 8, norm 0 or 1, tol and rtol finite and >= 0, rho 0 or in (0, 1)");
+  const CheckLoop loop{"cheby", "max_iters", "jacobi cheby check", o.tol, o.rtol, o.norm, o.max_iters,
+                       o.check_every == 0 ? 10 : o.check_every, o.lag, false};
+  loop.validate(o.rho == 0.0 || (std::isfinite(o.rho) && o.rho > 0.0 && o.rho < 1.0), ", rho 0 or in (0, 1)");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::cheby: the spectral radius is 1 on a periodic axis");
   cheby_setup();
-  const bool fixed = !(o.tol > 0.0) && !(o.rtol > 0.0);  // run exactly max_iters iterations
-  const int slots = o.lag + 1, last = o.max_iters / every;  // checks 0..last
   ChebyResult res;
   res.rho = o.rho == 0.0 ? cheby_rho(cfg_.nx_global, cfg_.ny_global) : o.rho;
   const double rho2 = res.rho * res.rho;
   double w = 1.0;  // the weight of the last iteration
-  int decided = 0;
-  bool stop = false;
   bool ring = false;  // the current buffer's 1-wide faces hold the neighbours' current values
   auto exchange = [&] {
     if (ring || fresh_[parity_]) return;
@@ -1307,23 +1299,6 @@ ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
       h.finish(s_);
     }
     ring = true;
-  };
-  auto decide = [&](int i) {
-    GMT_CHECK("cheby check", gmt_rt_event_synchronize(rn_ev_[i % slots]));
-    watchdog_kick("jacobi cheby check");
-    const double sum = rn_ring_[2 * (i % slots)], mx = rn_ring_[2 * (i % slots) + 1];
-    const double r = o.norm == 0 ? std::sqrt(sum) : mx;
-    res.residual_iters = i * every;
-    res.residual = r;
-    res.residual_max = mx;
-    if (i == 0) res.r0 = r;
-    if (!std::isfinite(sum) || !std::isfinite(mx)) {
-      res.failed = 1;
-      stop = true;
-    } else if (!fixed && r <= std::max(o.tol, o.rtol * res.r0)) {
-      res.converged = 1;
-      stop = true;
-    }
   };
   // iteration k + 1 of this call (k = 0: the plain sweep, w_1 = 1)
   auto iterate = [&](int k) {
@@ -1340,22 +1315,17 @@ ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
     ring = false;
   };
   int k = 0;
-  for (int i = 0; i <= last && !stop; ++i) {
-    if (i > 0) {
-      for (int j = 0; j < every; ++j) iterate(k++);
-      res.iters += every;
-      advanced_ = true;
-      watchdog_kick("jacobi cheby iterations enqueued");
-    }
-    exchange();
-    enqueue_residual(true);
-    GMT_CHECK("resid D2H", gmt_rt_memcpy_async(rn_ring_.data() + 2 * (i % slots), rn_dev_.data(),
-                                               2 * sizeof(double), s_));
-    GMT_CHECK("event", gmt_rt_event_record(rn_ev_[i % slots], s_));
-    res.checks = i + 1;
-    if (i >= o.lag) decide(decided++);
-  }
-  while (!stop && decided < res.checks) decide(decided++);
+  run_checks(loop, res,
+             [&] {
+               for (int j = 0; j < loop.every; ++j) iterate(k++);
+               advanced_ = true;
+               watchdog_kick("jacobi cheby iterations enqueued");
+             },
+             [&](int) {
+               exchange();
+               enqueue_residual(true);
+               return rn_dev_.data();
+             });
   if (res.iters > 0) fresh_[0] = fresh_[1] = false;  // only the faces of one buffer were exchanged
   synchronize();
   return res;

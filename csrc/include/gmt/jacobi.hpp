@@ -35,6 +35,7 @@
 // 16-B vector path; the row pitch is padded to 64 doubles.
 #pragma once
 
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -128,16 +129,19 @@ struct SolveOpts {
   int check_every = 0;           // sweeps between two checks (0 = tsteps)
   int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
 };
-struct SolveResult {
+// What solve(), cg() and cheby() report of their lagged checks.  An iteration
+// is a sweep for solve(), a CG or Chebyshev iteration for the other two.
+struct CheckResult {
   int converged = 0;        // the criterion was met
-  int sweeps = 0;           // sweeps advanced: residual_sweeps + lag * check_every unless the cap came first
+  int iters = 0;            // iterations run: residual_iters + lag * check_every unless the cap came first
   int checks = 0;           // checks enqueued
-  int residual_sweeps = 0;  // sweep count of the deciding check
-  double residual = 0.0;    // its residual in the chosen norm,
+  int residual_iters = 0;   // iteration count of the deciding check
+  double residual = 0.0;    // its residual in the chosen norm (cg: the recursive one),
   double residual_max = 0.0;  // its max |d|,
-  double r0 = 0.0;          // and the residual before any sweep (chosen norm)
-  int failed = 0;           // 1: a non-finite residual stopped the solve
+  double r0 = 0.0;          // and the residual of the starting field (chosen norm)
+  int failed = 0;           // 1: a non-finite residual stopped the iteration
 };
+using SolveResult = CheckResult;
 
 // JacobiSolver::cg: conjugate gradients on A u = b, A = I - J (J the Laplace
 // sweep; symmetric positive definite on a Dirichlet interior, the ring and the
@@ -150,17 +154,9 @@ struct CgOpts {
   int check_every = 0;           // iterations between two checks (0 = 10)
   int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
 };
-struct CgResult {
-  int converged = 0;        // the criterion was met
-  int iters = 0;            // iterations run: residual_iters + lag * check_every unless the cap came first
-  int checks = 0;           // checks enqueued
-  int residual_iters = 0;   // iteration count of the deciding check
-  double residual = 0.0;    // its (recursive) residual in the chosen norm,
-  double residual_max = 0.0;  // its max |r|,
-  double r0 = 0.0;          // and the residual of the starting field (chosen norm)
+struct CgResult : CheckResult {
   double true_residual = 0.0;      // residual_norm() of the final field: L2,
   double true_residual_max = 0.0;  // and max
-  int failed = 0;           // 1: a non-finite residual stopped the iteration
 };
 
 // JacobiSolver::cheby: Chebyshev semi-iteration over the sweep G (Golub-Varga),
@@ -181,16 +177,8 @@ struct ChebyOpts {
   // converges more slowly, an under-estimate can stagnate.
   double rho = 0.0;
 };
-struct ChebyResult {
-  int converged = 0;        // the criterion was met
-  int iters = 0;            // iterations run: residual_iters + lag * check_every unless the cap came first
-  int checks = 0;           // checks enqueued
-  int residual_iters = 0;   // iteration count of the deciding check
-  double residual = 0.0;    // its residual in the chosen norm,
-  double residual_max = 0.0;  // its max |d|,
-  double r0 = 0.0;          // and the residual of the starting field (chosen norm)
+struct ChebyResult : CheckResult {
   double rho = 0.0;         // the spectral radius used
-  int failed = 0;           // 1: a non-finite residual stopped the iteration
 };
 // 0.5*(cos(pi/(nx+1)) + cos(pi/(ny+1))): the spectral radius of the Laplace
 // sweep on an nx x ny interior with a zero ring
@@ -359,8 +347,14 @@ class JacobiSolver {
   // ring_current: the 1-wide faces of the current buffer were just exchanged
   void enqueue_residual(bool ring_current = false);
   void rn_setup();          // rn_ws_, rn_dev_, the ring and its events (first use)
+  void allreduce_sum_max(double* pair);  // {sum, max} -> the same bits on every rank
+  // the halo plan of the 1-wide faces around the interior of `field` (collective)
+  std::unique_ptr<Halo2D> faces_halo(double* field);
+  // the lagged check loop of solve(), cg() and cheby() (jacobi.cpp)
+  struct CheckLoop;
+  void run_checks(const CheckLoop& c, CheckResult& res, const std::function<void()>& advance,
+                  const std::function<const double*(int)>& check);
   void cg_setup();          // the state of cg() (first use; collective)
-  void cg_reduce(double* pair);  // all-reduce {sum, max} so every rank holds the same bits
   void cheby_setup();       // the halo plans of cheby() (first use; collective)
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over

@@ -4,12 +4,8 @@
 //
 //   cg_apply_walk    q = p - c0*((W+E)+(S+N))  (mode 0, + sum p*q)  or the
 //                    residual d of jacobi5_resid.hip (mode 1, + sum d^2 and
-//                    max |d|), 16 B/pt: jacobi5_resid_walk with a store — four
-//                    waves side by side on one row segment, one column pair per
-//                    lane, a three-row register window walked top-down, W/E
-//                    neighbours through DPP, one masked load for each column
-//                    outside the wave, xcd_swizzle so the rows two segments
-//                    share stay in one L2.
+//                    max |d|), 16 B/pt: the row walk of row_walk.hpp with one
+//                    16-B store per row.
 //   cg_update_k      x += a*p, r -= a*q, + sum r^2 and max |r|, 48 B/pt
 //   cg_dir_k         p = r + b*p, 24 B/pt
 //                    both streaming kernels in the shape of add2d_pt: one 16-B
@@ -30,6 +26,7 @@
 
 #include "common.hpp"
 #include "reduce_partials.hpp"
+#include "row_walk.hpp"
 #include "gmt/kernels.h"
 
 #ifndef GMT_CG_NT
@@ -46,12 +43,9 @@ __device__ __forceinline__ void cg_st2(double* p, d2 v) {
     st2(p, v);
 }
 
-constexpr int kCwWaveCols = 2 * kWave;                         // columns per wave
-constexpr int kCwBlockCols = kCwWaveCols * (kBlock / kWave);   // columns per workgroup
-// row loads in flight per lane (with f, two: its pairs double the registers of a row)
-constexpr int kCwUnrollP = 4, kCwUnrollF = 2;
-constexpr int64_t kCwMaxSeg = 256, kCwMinSeg = 8;
-constexpr int kCgRows = 4;                                     // rows per block of the streaming kernels
+// row loads in flight per lane of the walk (with f, two: its pairs double the registers of a row)
+constexpr int kCgUnrollP = 4, kCgUnrollF = 2;
+constexpr int kCgRows = 4;  // rows per block of the streaming kernels
 
 template <int MODE, bool HAS_F>
 __device__ __forceinline__ double cg_cell(double w, double e, double n, double s, double c, double c0, double c1,
@@ -92,6 +86,30 @@ __device__ __forceinline__ void cg_acc(double c, double v, bool on, double& acc,
   }
 }
 
+// the walk's op: a row is stored to q and accumulated
+template <int MODE, bool HAS_F>
+struct CgApplyOp {
+  double c0, c1;
+  double* __restrict__ q;
+  int64_t ldq;
+  double* pq = nullptr;
+  double acc = 0.0, m = 0.0;
+  __device__ __forceinline__ void begin(int64_t row, int64_t, int64_t xr) { pq = q + row * ldq + xr; }
+  __device__ __forceinline__ void load(int, int64_t) {}
+  __device__ __forceinline__ void row(int j, double w, double e, d2 a, d2 b, d2 c, d2 f, bool live, bool pair) {
+    d2 v;
+    v.x = cg_cell<MODE, HAS_F>(w, b.y, a.x, c.x, b.x, c0, c1, f.x);
+    v.y = cg_cell<MODE, HAS_F>(b.x, e, a.y, c.y, b.y, c0, c1, f.y);
+    if (pair)
+      cg_st2<0>(pq + j * ldq, v);
+    else if (live)
+      pq[j * ldq] = v.x;
+    cg_acc<MODE>(b.x, v.x, live, acc, m);
+    cg_acc<MODE>(b.y, v.y, pair, acc, m);
+  }
+  __device__ __forceinline__ void advance(int rows) { pq += rows * ldq; }
+};
+
 template <int MODE, bool HAS_F>
 __global__ __launch_bounds__(kBlock) void cg_apply_walk(int64_t x0, int64_t nx, int64_t y0, int64_t ny,
                                                         const double* __restrict__ u, int64_t ld,
@@ -99,73 +117,10 @@ __global__ __launch_bounds__(kBlock) void cg_apply_walk(int64_t x0, int64_t nx, 
                                                         double c1, double* __restrict__ q, int64_t ldq,
                                                         double* __restrict__ psum, double* __restrict__ pmax,
                                                         int64_t nseg, int64_t seg_rows, int64_t nblocks) {
-  const int64_t t = xcd_swizzle(blockIdx.x, nblocks);
-  const int64_t seg = t % nseg, bx = t / nseg;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int64_t xw = bx * kCwBlockCols + wave * kCwWaveCols;  // the wave's first column
-  constexpr int kCwUnroll = HAS_F ? kCwUnrollF : kCwUnrollP;
-  double acc = 0.0, m = 0.0;
-  if (xw < nx) {  // wave-uniform: every lane of a working wave stays active (DPP)
-    const int64_t r0 = seg * seg_rows;
-    const int64_t r1 = (r0 + seg_rows) < ny ? (r0 + seg_rows) : ny;
-    const int64_t xr = xw + 2 * lane;
-    const bool live = xr < nx, pair = xr + 1 < nx;
-    // lanes past the region re-read its last pair (their cells are masked and
-    // never stored); the lane of an odd last column loads the pair too: its
-    // second value is the cell's E neighbour
-    const int64_t xl = live ? xr : ((nx - 1) & ~int64_t(1));
-    const bool west = lane == 0;
-    const bool east = pair && (lane == kWave - 1 || xr + 2 >= nx);
-    const double* p = u + (y0 + r0 - 1) * ld + x0 + xl;
-    const double* pf = HAS_F ? f + (y0 + r0) * ldf + x0 + xl : nullptr;
-    double* pq = q + (y0 + r0) * ldq + x0 + xr;  // dereferenced by live lanes only
-    d2 a = ld2(p);  // row r - 1
-    p += ld;
-    d2 b = ld2(p);  // row r
-    for (int64_t r = r0; r < r1; r += kCwUnroll) {
-      const int64_t left = r1 - r;  // rows still to do, >= 1
-      d2 c[kCwUnroll], fv[kCwUnroll];
-      double ew[kCwUnroll], ee[kCwUnroll];
-#pragma unroll
-      for (int j = 0; j < kCwUnroll; ++j) {
-        // rows past the segment are clamped to its last ones (loaded, not used)
-        const int64_t oc = (j + 1 < left ? j + 1 : left) * ld;
-        const int64_t jr = j < left - 1 ? j : left - 1;
-        c[j] = ld2(p + oc);
-        ew[j] = ee[j] = 0.0;
-        if (west) ew[j] = p[jr * ld - 1];
-        if (east) ee[j] = p[jr * ld + 2];
-        if (HAS_F) fv[j] = ld2(pf + jr * ldf);
-      }
-#pragma unroll
-      for (int j = 0; j < kCwUnroll; ++j) {
-        if (j < left) {
-          const double wl = dpp_from_lower(b.y), eu = dpp_from_upper(b.x);
-          const double w = west ? ew[j] : wl, e = east ? ee[j] : eu;
-          d2 v;
-          v.x = cg_cell<MODE, HAS_F>(w, b.y, a.x, c[j].x, b.x, c0, c1, HAS_F ? fv[j].x : 0.0);
-          v.y = cg_cell<MODE, HAS_F>(b.x, e, a.y, c[j].y, b.y, c0, c1, HAS_F ? fv[j].y : 0.0);
-          if (pair)
-            cg_st2<0>(pq + j * ldq, v);
-          else if (live)
-            pq[j * ldq] = v.x;
-          cg_acc<MODE>(b.x, v.x, live, acc, m);
-          cg_acc<MODE>(b.y, v.y, pair, acc, m);
-        }
-        a = b;
-        b = c[j];
-      }
-      p += kCwUnroll * ld;
-      pq += kCwUnroll * ldq;
-      if (HAS_F) pf += kCwUnroll * ldf;
-    }
-  }
-  acc = block_sum(acc);
-  m = block_max(m);
-  if (threadIdx.x == 0) {
-    psum[blockIdx.x] = acc;
-    pmax[blockIdx.x] = m;
-  }
+  constexpr int kUnroll = HAS_F ? kCgUnrollF : kCgUnrollP;
+  CgApplyOp<MODE, HAS_F> op{c0, c1, q, ldq};
+  row_walk<kUnroll, HAS_F>(x0, nx, y0, ny, u, ld, f, ldf, nseg, seg_rows, nblocks, op);
+  write_block_partials(op.acc, op.m, psum, pmax);
 }
 
 template <int MODE, bool HAS_F>
@@ -184,12 +139,7 @@ __global__ __launch_bounds__(kBlock) void cg_apply_scalar(int64_t x0, int64_t nx
     q[y * ldq + x] = v;
     cg_acc<MODE>(pc[0], v, true, acc, m);
   }
-  acc = block_sum(acc);
-  m = block_max(m);
-  if (threadIdx.x == 0) {
-    psum[blockIdx.x] = acc;
-    pmax[blockIdx.x] = m;
-  }
+  write_block_partials(acc, m, psum, pmax);
 }
 
 // PT: the lane's column pair (a scalar last column of an odd nx); else one column per lane
@@ -238,12 +188,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_k(int64_t x0, int64_t nx, in
       }
     }
   }
-  acc = block_sum(acc);
-  m = block_max(m);
-  if (threadIdx.x == 0) {
-    psum[blockIdx.x] = acc;
-    pmax[blockIdx.x] = m;
-  }
+  write_block_partials(acc, m, psum, pmax);
 }
 
 template <bool PT>
@@ -276,26 +221,6 @@ __global__ __launch_bounds__(kBlock) void cg_dir_k(int64_t x0, int64_t nx, int64
   }
 }
 
-// Rows per segment of the row walk: jacobi5_resid.hip's rule (as long as
-// possible while the launch still has 8 workgroups per compute unit)
-static int64_t cg_seg_rows(int64_t nx, int64_t ny) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  const int64_t nbx = (nx + kCwBlockCols - 1) / kCwBlockCols;
-  int64_t L = kCwMaxSeg;
-  while (L > kCwMinSeg && nbx * ((ny + L - 1) / L) < 8 * static_cast<int64_t>(cus)) L /= 2;
-  return L;
-}
-static int64_t cg_walk_blocks(int64_t nx, int64_t ny, int64_t* nseg, int64_t* seg_rows) {
-  *seg_rows = cg_seg_rows(nx, ny);
-  *nseg = (ny + *seg_rows - 1) / *seg_rows;
-  return ((nx + kCwBlockCols - 1) / kCwBlockCols) * *nseg;
-}
 // blocks of the streaming kernels: nbx per row group
 static int64_t cg_stream_blocks(bool pt, int64_t nx, int64_t ny, int64_t* nbx) {
   const int64_t cols = pt ? 2 * kBlock : kBlock;
@@ -305,27 +230,27 @@ static int64_t cg_stream_blocks(bool pt, int64_t nx, int64_t ny, int64_t* nbx) {
 // the most partials any of the kernels writes for this region
 static int64_t cg_max_blocks(int64_t nx, int64_t ny) {
   int64_t nseg, L, nbx;
-  int64_t n = cg_walk_blocks(nx, ny, &nseg, &L);
+  int64_t n = walk_blocks(nx, ny, &nseg, &L);
   n = std::max(n, (nx * ny + kBlock - 1) / kBlock);
   n = std::max(n, cg_stream_blocks(true, nx, ny, &nbx));
   n = std::max(n, cg_stream_blocks(false, nx, ny, &nbx));
   return n;
 }
-static bool cg_vec_ok(const double* a, int64_t ld) { return aligned16(a) && ld % 2 == 0; }
 
 static int cg_apply_path(int64_t x0, const double* p, int64_t ldp, const double* f, int64_t ldf, const double* q,
                          int64_t ldq) {
-  return x0 % 2 == 0 && cg_vec_ok(p, ldp) && cg_vec_ok(q, ldq) && (!f || cg_vec_ok(f, ldf)) ? GMT_PATH_ROW_WALK
-                                                                                          : GMT_PATH_SCALAR;
+  return x0 % 2 == 0 && walk_vec_ok(p, ldp) && walk_vec_ok(q, ldq) && (!f || walk_vec_ok(f, ldf))
+             ? GMT_PATH_ROW_WALK
+             : GMT_PATH_SCALAR;
 }
 static int cg_update_path(int64_t x0, const double* p, int64_t ldp, const double* q, int64_t ldq, const double* x,
                           int64_t ldx, const double* r, int64_t ldr) {
-  return x0 % 2 == 0 && cg_vec_ok(p, ldp) && cg_vec_ok(q, ldq) && cg_vec_ok(x, ldx) && cg_vec_ok(r, ldr)
+  return x0 % 2 == 0 && walk_vec_ok(p, ldp) && walk_vec_ok(q, ldq) && walk_vec_ok(x, ldx) && walk_vec_ok(r, ldr)
              ? GMT_PATH_PT
              : GMT_PATH_SCALAR;
 }
 static int cg_dir_path(int64_t x0, const double* r, int64_t ldr, const double* p, int64_t ldp) {
-  return x0 % 2 == 0 && cg_vec_ok(r, ldr) && cg_vec_ok(p, ldp) ? GMT_PATH_PT : GMT_PATH_SCALAR;
+  return x0 % 2 == 0 && walk_vec_ok(r, ldr) && walk_vec_ok(p, ldp) ? GMT_PATH_PT : GMT_PATH_SCALAR;
 }
 
 template <int MODE, bool HAS_F>
@@ -334,7 +259,7 @@ static void cg_apply_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64
                             int64_t ldq, double* psum, double* pmax, int64_t* nb, hipStream_t s) {
   if (walk) {
     int64_t nseg, L;
-    *nb = cg_walk_blocks(nx, ny, &nseg, &L);
+    *nb = walk_blocks(nx, ny, &nseg, &L);
     cg_apply_walk<MODE, HAS_F><<<grid_1d(*nb), kBlock, 0, s>>>(x0, nx, y0, ny, p, ldp, f, ldf, c0, c1, q, ldq, psum,
                                                                pmax, nseg, L, *nb);
   } else {
@@ -357,7 +282,7 @@ extern "C" int gmt_cg_apply_path(int64_t x0, int64_t nx, int64_t ny, const doubl
                                  const double* f, int64_t ldf, const double* q, int64_t ldq, int64_t* seg_rows) {
   using namespace gmt;
   const int path = cg_apply_path(x0, p, ldp, f, ldf, q, ldq);
-  if (seg_rows) *seg_rows = path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0 ? cg_seg_rows(nx, ny) : 0;
+  if (seg_rows) *seg_rows = path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0 ? walk_seg_rows(nx, ny) : 0;
   return path;
 }
 extern "C" int gmt_cg_update_path(int64_t x0, const double* p, int64_t ldp, const double* q, int64_t ldq,
@@ -391,8 +316,7 @@ extern "C" int gmt_cg_apply(int mode, int64_t x0, int64_t nx, int64_t y0, int64_
     cg_apply_launch<1, true>(walk, x0, nx, y0, ny, p, ldp, f, ldf, c0, c1, q, ldq, psum, pmax, &nb, s);
   else
     cg_apply_launch<1, false>(walk, x0, nx, y0, ny, p, ldp, f, ldf, c0, c1, q, ldq, psum, pmax, &nb, s);
-  reduce_partials<0>(psum, nb, out, s);
-  reduce_partials<1>(pmax, nb, out + 1, s);
+  reduce_sum_max(psum, pmax, nb, out, s);
   GMT_RET_LAUNCH();
 }
 
@@ -419,8 +343,7 @@ extern "C" int gmt_cg_update(int64_t x0, int64_t nx, int64_t y0, int64_t ny, con
   else
     cg_update_k<false><<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, num, den, p, ldp, q, ldq, x, ldx, r, ldr, psum,
                                                       pmax, static_cast<unsigned>(nbx));
-  reduce_partials<0>(psum, nb, out, s);
-  reduce_partials<1>(pmax, nb, out + 1, s);
+  reduce_sum_max(psum, pmax, nb, out, s);
   GMT_RET_LAUNCH();
 }
 

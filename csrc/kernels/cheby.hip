@@ -7,13 +7,8 @@
 // u is the current iterate, v the previous one, overwritten in place by the
 // next; w is the iteration's weight, passed by value.
 //
-//   cheby_step_walk    the row walk of cg_apply_walk / jacobi5_resid_walk: four
-//                      waves side by side on one row segment, one column pair
-//                      per lane, a three-row register window of u walked
-//                      top-down, W/E neighbours through DPP, one masked load
-//                      for each column outside the wave, xcd_swizzle so the
-//                      rows two segments share stay in one L2.  Each row adds
-//                      one 16-B load of v (and of f), issued with that row's u
+//   cheby_step_walk    the row walk of row_walk.hpp over u.  Each row adds one
+//                      16-B load of v (and of f), issued with that row's u
 //                      loads, and one 16-B store of v': 24 B/pt (32 with f).
 //                      No reductions, no workspace.
 //   cheby_step_scalar  one cell per lane, for odd alignment or pitches.
@@ -25,6 +20,7 @@
 // rebuilds the file with another policy for the A/B recorded in
 // profiles/cheby/README.md.
 #include "common.hpp"
+#include "row_walk.hpp"
 #include "gmt/kernels.h"
 
 #ifndef GMT_CHEBY_NT
@@ -33,11 +29,8 @@
 
 namespace gmt {
 
-constexpr int kChWaveCols = 2 * kWave;                        // columns per wave
-constexpr int kChBlockCols = kChWaveCols * (kBlock / kWave);  // columns per workgroup
 // row loads in flight per lane (with f, two: its pairs add a third of the registers of a row)
-constexpr int kChUnrollP = 4, kChUnrollF = 2;
-constexpr int64_t kChMaxSeg = 256, kChMinSeg = 8;
+constexpr int kChebyUnrollP = 4, kChebyUnrollF = 2;
 
 template <bool HAS_F>
 __device__ __forceinline__ double cheby_cell(double w, double e, double n, double s, double v, double c0, double c1,
@@ -58,6 +51,36 @@ __device__ __forceinline__ void cheby_stv(double* p, d2 v) {
     st2(p, v);
 }
 
+// the walk's op: a row loads its pair of v with its loads of u and stores v'
+// over it (the second value a lane of an odd last column loads is unused)
+template <bool HAS_F, int UNROLL>
+struct ChebyOp {
+  double c0, c1, om;
+  double* __restrict__ v;
+  int64_t ldv;
+  const double* pv;  // loads: the clamped column
+  double* po;        // stores: the lane's own column
+  d2 vv[UNROLL];
+  __device__ __forceinline__ void begin(int64_t row, int64_t xl, int64_t xr) {
+    pv = v + row * ldv + xl;
+    po = v + row * ldv + xr;
+  }
+  __device__ __forceinline__ void load(int j, int64_t jr) { vv[j] = cheby_ldv(pv + jr * ldv); }
+  __device__ __forceinline__ void row(int j, double w, double e, d2 a, d2 b, d2 c, d2 f, bool live, bool pair) {
+    d2 o;
+    o.x = cheby_cell<HAS_F>(w, b.y, a.x, c.x, vv[j].x, c0, c1, f.x, om);
+    o.y = cheby_cell<HAS_F>(b.x, e, a.y, c.y, vv[j].y, c0, c1, f.y, om);
+    if (pair)
+      cheby_stv(po + j * ldv, o);
+    else if (live)
+      po[j * ldv] = o.x;
+  }
+  __device__ __forceinline__ void advance(int rows) {
+    pv += rows * ldv;
+    po += rows * ldv;
+  }
+};
+
 template <bool HAS_F>
 __global__ __launch_bounds__(kBlock) void cheby_step_walk(int64_t x0, int64_t nx, int64_t y0, int64_t ny,
                                                           const double* __restrict__ u, int64_t ld,
@@ -65,66 +88,9 @@ __global__ __launch_bounds__(kBlock) void cheby_step_walk(int64_t x0, int64_t nx
                                                           double c1, double om, double* __restrict__ v,
                                                           int64_t ldv, int64_t nseg, int64_t seg_rows,
                                                           int64_t nblocks) {
-  const int64_t t = xcd_swizzle(blockIdx.x, nblocks);
-  const int64_t seg = t % nseg, bx = t / nseg;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int64_t xw = bx * kChBlockCols + wave * kChWaveCols;  // the wave's first column
-  constexpr int kUnroll = HAS_F ? kChUnrollF : kChUnrollP;
-  if (xw >= nx) return;  // wave-uniform: every lane of a working wave stays active (DPP)
-  const int64_t r0 = seg * seg_rows;
-  const int64_t r1 = (r0 + seg_rows) < ny ? (r0 + seg_rows) : ny;
-  const int64_t xr = xw + 2 * lane;
-  const bool live = xr < nx, pair = xr + 1 < nx;
-  // lanes past the region re-read its last pair (their cells are masked and
-  // never stored); the lane of an odd last column loads the pair too: its
-  // second value of u is the cell's E neighbour, that of v and f is unused
-  const int64_t xl = live ? xr : ((nx - 1) & ~int64_t(1));
-  const bool west = lane == 0;
-  const bool east = pair && (lane == kWave - 1 || xr + 2 >= nx);
-  const double* p = u + (y0 + r0 - 1) * ld + x0 + xl;
-  const double* pf = HAS_F ? f + (y0 + r0) * ldf + x0 + xl : nullptr;
-  const double* pv = v + (y0 + r0) * ldv + x0 + xl;
-  double* po = v + (y0 + r0) * ldv + x0 + xr;  // dereferenced by live lanes only
-  d2 a = ld2(p);  // row r - 1
-  p += ld;
-  d2 b = ld2(p);  // row r
-  for (int64_t r = r0; r < r1; r += kUnroll) {
-    const int64_t left = r1 - r;  // rows still to do, >= 1
-    d2 c[kUnroll], vv[kUnroll], fv[kUnroll];
-    double ew[kUnroll], ee[kUnroll];
-#pragma unroll
-    for (int j = 0; j < kUnroll; ++j) {
-      // rows past the segment are clamped to its last ones (loaded, not used)
-      const int64_t oc = (j + 1 < left ? j + 1 : left) * ld;
-      const int64_t jr = j < left - 1 ? j : left - 1;
-      c[j] = ld2(p + oc);
-      ew[j] = ee[j] = 0.0;
-      if (west) ew[j] = p[jr * ld - 1];
-      if (east) ee[j] = p[jr * ld + 2];
-      vv[j] = cheby_ldv(pv + jr * ldv);
-      if (HAS_F) fv[j] = ld2(pf + jr * ldf);
-    }
-#pragma unroll
-    for (int j = 0; j < kUnroll; ++j) {
-      if (j < left) {
-        const double wl = dpp_from_lower(b.y), eu = dpp_from_upper(b.x);
-        const double w = west ? ew[j] : wl, e = east ? ee[j] : eu;
-        d2 o;
-        o.x = cheby_cell<HAS_F>(w, b.y, a.x, c[j].x, vv[j].x, c0, c1, HAS_F ? fv[j].x : 0.0, om);
-        o.y = cheby_cell<HAS_F>(b.x, e, a.y, c[j].y, vv[j].y, c0, c1, HAS_F ? fv[j].y : 0.0, om);
-        if (pair)
-          cheby_stv(po + j * ldv, o);
-        else if (live)
-          po[j * ldv] = o.x;
-      }
-      a = b;
-      b = c[j];
-    }
-    p += kUnroll * ld;
-    pv += kUnroll * ldv;
-    po += kUnroll * ldv;
-    if (HAS_F) pf += kUnroll * ldf;
-  }
+  constexpr int kUnroll = HAS_F ? kChebyUnrollF : kChebyUnrollP;
+  ChebyOp<HAS_F, kUnroll> op{c0, c1, om, v, ldv};
+  row_walk<kUnroll, HAS_F>(x0, nx, y0, ny, u, ld, f, ldf, nseg, seg_rows, nblocks, op);
 }
 
 template <bool HAS_F>
@@ -141,26 +107,9 @@ __global__ __launch_bounds__(kBlock) void cheby_step_scalar(int64_t x0, int64_t 
   *pv = cheby_cell<HAS_F>(pc[-1], pc[1], pc[-ld], pc[ld], *pv, c0, c1, HAS_F ? f[y * ldf + x] : 0.0, om);
 }
 
-// Rows per segment of the row walk: jacobi5_resid.hip's rule (as long as
-// possible while the launch still has 8 workgroups per compute unit)
-static int64_t cheby_seg_rows(int64_t nx, int64_t ny) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  const int64_t nbx = (nx + kChBlockCols - 1) / kChBlockCols;
-  int64_t L = kChMaxSeg;
-  while (L > kChMinSeg && nbx * ((ny + L - 1) / L) < 8 * static_cast<int64_t>(cus)) L /= 2;
-  return L;
-}
-static bool cheby_vec_ok(const double* a, int64_t ld) { return aligned16(a) && ld % 2 == 0; }
-
 static int cheby_path(int64_t x0, const double* u, int64_t ld, const double* f, int64_t ldf, const double* v,
                       int64_t ldv) {
-  return x0 % 2 == 0 && cheby_vec_ok(u, ld) && cheby_vec_ok(v, ldv) && (!f || cheby_vec_ok(f, ldf))
+  return x0 % 2 == 0 && walk_vec_ok(u, ld) && walk_vec_ok(v, ldv) && (!f || walk_vec_ok(f, ldf))
              ? GMT_PATH_ROW_WALK
              : GMT_PATH_SCALAR;
 }
@@ -170,8 +119,8 @@ static int cheby_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64_t n
                         const double* f, int64_t ldf, double c0, double c1, double om, double* v, int64_t ldv,
                         hipStream_t s) {
   if (walk) {
-    const int64_t L = cheby_seg_rows(nx, ny), nseg = (ny + L - 1) / L;
-    const int64_t nb = ((nx + kChBlockCols - 1) / kChBlockCols) * nseg;
+    int64_t nseg, L;
+    const int64_t nb = walk_blocks(nx, ny, &nseg, &L);
     if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
     cheby_step_walk<HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, om, v, ldv, nseg, L,
                                                           nb);
@@ -189,7 +138,7 @@ extern "C" int gmt_cheby_step_path(int64_t x0, int64_t nx, int64_t ny, const dou
                                    int64_t ldf, const double* v, int64_t ldv, int64_t* seg_rows) {
   using namespace gmt;
   const int path = cheby_path(x0, u, ld, f, ldf, v, ldv);
-  if (seg_rows) *seg_rows = path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0 ? cheby_seg_rows(nx, ny) : 0;
+  if (seg_rows) *seg_rows = path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0 ? walk_seg_rows(nx, ny) : 0;
   return path;
 }
 

@@ -54,4 +54,10 @@ static void reduce_partials(const double* partial, int64_t nb, double* out, hipS
   reduce_all<OP><<<1, kBlock, 0, s>>>(l2, used, out);
 }
 
+// the block partials of write_block_partials (row_walk.hpp) -> out[0] = sum, out[1] = max
+static void reduce_sum_max(const double* psum, const double* pmax, int64_t nb, double* out, hipStream_t s) {
+  reduce_partials<0>(psum, nb, out, s);
+  reduce_partials<1>(pmax, nb, out + 1, s);
+}
+
 }  // namespace gmt

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import kernel_refs as kr
+import resid_cases as rc
 from gpu_mpi_tests_amd import _native, ops
 from gpu_mpi_tests_amd.ops import reference as ref
 
@@ -237,3 +238,20 @@ def test_jacobi5_path_scalar_for_odd_origin_or_pitch():
     v = torch.zeros(8, 41, dtype=F64, device=DEV)
     assert ops.jacobi5_path(v, v, (4, 31, 2, 4)) == ops.PATH_SCALAR
     assert ops.jacobi5_path(u, u, (4, 31, 2, 4), f=v) == ops.PATH_SCALAR
+
+
+# ------------------------------------------------- the row walk's segment rule (row_walk.hpp)
+@pytest.mark.parametrize("ny", [1, 9, 256, 513])
+@pytest.mark.parametrize("nx", [rc.NXS[0], rc.NXS[4], rc.NXS[5], rc.NXS[-1]])
+def test_row_walk_kernels_agree_on_seg_rows(nx, ny):
+    """The residual, CG's apply and the Chebyshev step walk the same segments:
+    one rule decides the rows per segment of all three."""
+    u = torch.zeros(ny + 2, 8 + nx + 1 + (nx + 1) % 2, dtype=F64, device=DEV)
+    v = torch.zeros_like(u)
+    region = (8, nx, 1, ny)
+    resid = ops.jacobi5_resid_path(u, region)
+    assert resid[0] == ops.PATH_ROW_WALK and resid[1] >= 2
+    assert ops.cg_apply_path(u, v, region) == resid
+    assert ops.cheby_step_path(u, v, region) == resid
+    assert ops.jacobi5_resid_path(u, region, f=v) == ops.cg_apply_path(u, v, region, v) == resid
+    assert ops.cheby_step_path(u, v, region, v) == resid
