@@ -20,6 +20,9 @@
 //      --only=cg [--reps=5] [--cg-n=N]: the three launches of a conjugate-gradient
 //      iteration (gmt_cg_apply 16 B/point, gmt_cg_update 48, gmt_cg_dir 24), each
 //      alternated with gmt_daxpy on the same element count
+//      --only=mg [--reps=5] [--mg-n=N]: the kernels of a multigrid cycle
+//      (gmt_mg_smooth 16 B/fine point, 24 with f, gmt_mg_restrict 10,
+//      gmt_mg_prolong_add 18) on N x N (odd, default 8191), as --only=cg
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -492,6 +495,68 @@ int main(int argc, char** argv) {
       report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
       report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
       std::printf("cheby %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
+                  (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
+    }
+  }
+  if (only.find("mg") != std::string::npos) {
+    // --only=mg: the three kernels of a JacobiSolver::mg cycle (gmt_mg_smooth
+    // without and with f, gmt_mg_restrict, gmt_mg_prolong_add) on a fine level
+    // of n x n (default 8191) and its (n-1)/2 coarse level, in the engine's
+    // layout, each against gmt_daxpy on n * n contiguous elements, --reps=5
+    // rounds in the order A B B A; the best of the rounds is compared.  GB/s
+    // from the compulsory bytes per fine point: smooth 16 (24 with f), restrict
+    // 8 + 2, prolong_add 16 + 2.
+    const int reps = static_cast<int>(cli.geti("reps", 5));
+    const int64_t n = cli.geti("mg-n", 8191), m = (n - 1) / 2;
+    if (n < 3 || n % 2 == 0) {
+      std::printf("ERROR: --mg-n must be odd and >= 3\n");
+      return 1;
+    }
+    const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64, ldc = ((xo + m + 1 + 63) / 64) * 64;
+    const size_t elems = static_cast<size_t>(ld) * (n + 2), celems = static_cast<size_t>(ldc) * (m + 2);
+    Buffer<double> u(elems, GMT_SPACE_DEVICE), v(elems, GMT_SPACE_DEVICE), f(elems, GMT_SPACE_DEVICE),
+        e(celems, GMT_SPACE_DEVICE);
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, u.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, v.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(3, ld, n + 2, 0.0, 1e-9, 0.0, 0.0, f.data(), ld, s));
+    GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
+    GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+    int64_t seg = 0, segf = 0;
+    const int path = gmt_mg_smooth_path(xo, n, n, u.data(), ld, nullptr, 0, v.data(), ld, &seg);
+    const int pathf = gmt_mg_smooth_path(xo, n, n, u.data(), ld, f.data(), ld, v.data(), ld, &segf);
+    std::printf("mg %lldx%lld  smooth path %d (%lld rows per segment), with f %d (%lld), restrict path %d, prolong path "
+                "%d, pitch %lld, coarse %lldx%lld pitch %lld\n", (long long)n, (long long)n, path, (long long)seg, pathf,
+                (long long)segf, gmt_mg_restrict_path(xo, xo, u.data(), ld, e.data(), ldc),
+                gmt_mg_prolong_add_path(xo, e.data(), ldc, v.data(), ld), (long long)ld, (long long)m, (long long)m,
+                (long long)ldc);
+    // prolong_add adds a field of 1e-12 a call: v stays bounded over the repeats
+    const std::function<void()> kernel[4] = {
+        [&] { GMT_CHECK("mg_smooth", gmt_mg_smooth(xo, n, 1, n, u.data(), ld, nullptr, 0, 0.25, 0.0, 0.8, v.data(), ld,
+                                                   s)); },
+        [&] { GMT_CHECK("mg_smooth_f", gmt_mg_smooth(xo, n, 1, n, u.data(), ld, f.data(), ld, 0.25, 1.0, 0.8, v.data(),
+                                                     ld, s)); },
+        [&] { GMT_CHECK("mg_restrict", gmt_mg_restrict(xo, n, 1, n, 1, 1, u.data(), ld, 0.25, e.data(), xo, 1, ldc, s)); },
+        [&] { GMT_CHECK("mg_prolong_add", gmt_mg_prolong_add(xo, n, 1, n, 1, 1, e.data(), xo, 1, ldc, v.data(), ld, s)); }};
+    const std::function<void()> daxpy = [&] { GMT_CHECK("daxpy", gmt_daxpy(n * n, 1e-3, f.data(), u.data(), s)); };
+    const char* name[4] = {"mg_smooth", "mg_smooth_f", "mg_restrict", "mg_prolong_add"};
+    const double bytes[4] = {16.0, 24.0, 10.0, 18.0};
+    for (int k = 0; k < 4; ++k) {
+      if (k == 3) GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
+      Stats st[2];
+      const int order[4] = {0, 1, 1, 0};
+      for (int rep = 0; rep < reps; ++rep)
+        for (int o = 0; o < 4; ++o) {
+          const int w = order[o];
+          const double ms = time_ms(s, iters, w == 0 ? kernel[k] : daxpy);
+          st[w].add(ms);
+          std::printf("mg %lldx%lld rep %d  %-14s %9.4f ms\n", (long long)n, (long long)n, rep,
+                      w == 0 ? name[k] : "daxpy", ms);
+        }
+      char shape[64];
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+      report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
+      report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
+      std::printf("mg %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
                   (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
     }
   }

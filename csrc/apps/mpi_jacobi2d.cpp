@@ -58,6 +58,15 @@
 //                           converges more slowly, an under-estimate can stagnate).  --check runs
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
+//   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C]
+//                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
+//                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
+//                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
+//                           cycle cap; A / B damped Jacobi sweeps before / after the correction
+//                           (default 2,2), W their damping (default 0.8), N the number of levels
+//                           (default: all), C the Chebyshev iterations on the coarsest level
+//                           (default: from its spectral radius).  --check runs the same number of
+//                           serial cycles and compares within 1e-10 * max|u0|
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -65,6 +74,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -237,6 +247,113 @@ static std::vector<double> serial_cheby(int64_t ny, int64_t nx, int iters, doubl
   return out;
 }
 
+// Serial multigrid V-cycles on the whole Dirichlet problem, the definition of
+// JacobiSolver::mg (gmt/jacobi.hpp): `cycles` cycles from the initial field on
+// `levels` levels, every cell in the kernels' order (csrc/kernels/mg.hip).
+// Fields carry a 1-wide ring: the real one on the fine level, zero below it.
+static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const MgOpts& o, int levels, int coarse_iters,
+                                     double coarse_rho, int source, double amp, uint64_t seed, int init,
+                                     double* umax) {
+  struct Level {
+    int64_t ny, nx, ld;
+    std::vector<double> u[2], s, d;
+    bool has_s;
+  };
+  std::vector<Level> lv(levels);
+  for (int l = 0; l < levels; ++l) {
+    Level& v = lv[l];
+    v.ny = l == 0 ? ny : (lv[l - 1].ny - 1) / 2;
+    v.nx = l == 0 ? nx : (lv[l - 1].nx - 1) / 2;
+    v.ld = v.nx + 2;
+    v.has_s = l > 0 || source != 0;
+    for (auto* f : {&v.u[0], &v.u[1], &v.s, &v.d}) f->assign((v.ny + 2) * v.ld, 0.0);
+  }
+  lv[0].u[0] = serial_init(ny, nx, init, seed);
+  lv[0].u[1] = lv[0].u[0];
+  *umax = 0;
+  for (double v : lv[0].u[0]) *umax = std::fmax(*umax, std::fabs(v));
+  if (source != 0) {
+    const std::vector<double> src = serial_source(ny, nx, source, amp, seed);
+    for (int64_t j = 0; j < ny; ++j)
+      for (int64_t i = 0; i < nx; ++i) lv[0].s[(j + 1) * lv[0].ld + i + 1] = src[j * nx + i];
+  }
+  const double rho2 = coarse_rho * coarse_rho;
+  std::function<int(int, int)> cycle = [&](int l, int cur) -> int {
+    Level& v = lv[l];
+    const int64_t ld = v.ld;
+    auto sweep = [&](const std::vector<double>& u, int64_t k) {
+      const double* c = &u[k];
+      double g = 0.25 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+      if (v.has_s) g = g + 1.0 * v.s[k];
+      return g;
+    };
+    // out = c + w*(G(u) - c) over the interior, each operation rounded once
+    auto relax = [&](double w, bool from_other) {
+      const std::vector<double>& u = v.u[cur];
+      std::vector<double>& out = v.u[cur ^ 1];
+      for (int64_t j = 1; j <= v.ny; ++j)
+        for (int64_t i = 1; i <= v.nx; ++i) {
+          const int64_t k = j * ld + i;
+          const double c = from_other ? out[k] : u[k];
+          volatile double t = sweep(u, k) - c;
+          t = w * t;
+          out[k] = c + t;
+        }
+      cur ^= 1;
+    };
+    if (l == levels - 1) {  // Chebyshev from zero; the first iteration is the plain sweep
+      double w = 1.0;
+      for (int k = 0; k < coarse_iters; ++k) {
+        if (k > 0) w = cheby_next_weight(rho2, w, k);
+        if (k == 0) {
+          for (int64_t j = 1; j <= v.ny; ++j)
+            for (int64_t i = 1; i <= v.nx; ++i) v.u[cur ^ 1][j * ld + i] = sweep(v.u[cur], j * ld + i);
+          cur ^= 1;
+        } else {
+          relax(w, true);
+        }
+      }
+      return cur;
+    }
+    for (int i = 0; i < o.nu1; ++i) relax(o.omega, false);
+    for (int64_t j = 1; j <= v.ny; ++j)
+      for (int64_t i = 1; i <= v.nx; ++i) v.d[j * ld + i] = sweep(v.u[cur], j * ld + i) - v.u[cur][j * ld + i];
+    Level& c = lv[l + 1];
+    auto h = [&](int64_t k) { return (v.d[k - 1] + v.d[k + 1]) + 2.0 * v.d[k]; };
+    for (int64_t J = 1; J <= c.ny; ++J)
+      for (int64_t I = 1; I <= c.nx; ++I) {
+        const int64_t k = 2 * J * ld + 2 * I;  // coarse point (J-1, I-1) sits on fine interior point (2J-1, 2I-1)
+        c.s[J * c.ld + I] = 0.25 * ((h(k - ld) + h(k + ld)) + 2.0 * h(k));
+      }
+    std::fill(c.u[0].begin(), c.u[0].end(), 0.0);
+    const std::vector<double>& e = c.u[cycle(l + 1, 0)];
+    std::vector<double>& u = v.u[cur];
+    for (int64_t j = 1; j <= v.ny; ++j)
+      for (int64_t i = 1; i <= v.nx; ++i) {
+        const bool ony = j % 2 == 0, onx = i % 2 == 0;
+        const double* p = &e[(ony ? j / 2 : (j - 1) / 2) * c.ld + (onx ? i / 2 : (i - 1) / 2)];
+        double t;
+        if (onx && ony)
+          t = p[0];
+        else if (ony)
+          t = 0.5 * (p[0] + p[1]);
+        else if (onx)
+          t = 0.5 * (p[0] + p[c.ld]);
+        else
+          t = 0.25 * ((p[0] + p[1]) + (p[c.ld] + p[c.ld + 1]));
+        u[j * ld + i] = u[j * ld + i] + t;
+      }
+    for (int i = 0; i < o.nu2; ++i) relax(o.omega, false);
+    return cur;
+  };
+  int cur = 0;
+  for (int k = 0; k < cycles; ++k) cur = cycle(0, cur);
+  std::vector<double> out(ny * nx);
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) out[j * nx + i] = lv[0].u[cur][(j + 1) * lv[0].ld + i + 1];
+  return out;
+}
+
 int main(int argc, char** argv) {
   Cli cli(argc, argv);
   int64_t n = cli.positional(0) ? std::atoll(cli.positional(0)) : 8192;
@@ -328,8 +445,44 @@ int main(int argc, char** argv) {
     std::fflush(stdout);
     MPI_Abort(MPI_COMM_WORLD, 1);
   }
-  const bool cg_mode = cli.flag("cg") || cheby_mode;
-  const char* mode_name = cheby_mode ? "--cheby" : "--cg";
+  // mg_mode picks JacobiSolver::mg: a cycle is its iteration
+  const bool mg_mode = cli.flag("mg");
+  if (mg_mode && (cheby_mode || cli.flag("cg"))) {
+    if (rank == 0) std::printf("ERROR: --mg is exclusive with --cg and --cheby\n");
+    std::fflush(stdout);
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
+  const bool cg_mode = cli.flag("cg") || cheby_mode || mg_mode;
+  const char* mode_name = mg_mode ? "--mg" : (cheby_mode ? "--cheby" : "--cg");
+  MgOpts mo;
+  MgResult mr;
+  if (mg_mode) {
+    const std::string nu = cli.get("nu", "2,2");
+    const bool nu_ok = std::sscanf(nu.c_str(), "%d,%d", &mo.nu1, &mo.nu2) == 2;
+    mo.omega = std::atof(cli.get("omega", "0.8").c_str());
+    mo.max_levels = static_cast<int>(cli.geti("levels", 0));
+    mo.coarse_iters = static_cast<int>(cli.geti("coarse-iters", 0));
+    if (!nu_ok || mo.nu1 < 0 || mo.nu2 < 0 || mo.nu1 + mo.nu2 == 0 || !(mo.omega > 0 && mo.omega <= 1) ||
+        mo.max_levels < 0 || mo.max_levels == 1 || mo.coarse_iters < 0) {
+      if (rank == 0)
+        std::printf("ERROR: --mg needs --nu=A,B (A, B >= 0, A + B > 0), --omega in (0, 1], --levels 0 or >= 2 and "
+                    "--coarse-iters >= 0\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    if (!c.periodic && mg_level_table(c.ny_global, c.nx_global, c.py, c.px, mo.max_levels).size() < 2) {
+      if (rank == 0) {
+        if (c.ny_global % 2 == 0 || c.nx_global % 2 == 0)
+          std::printf("ERROR: --mg has no coarse level for %lld x %lld: nx + 1 and ny + 1 must be even (8191 and "
+                      "32767 coarsen, 8192 does not)\n", (long long)c.ny_global, (long long)c.nx_global);
+        else
+          std::printf("ERROR: --mg has no coarse level for %lld x %lld on a %dx%d grid: a rank would own no coarse "
+                      "point\n", (long long)c.ny_global, (long long)c.nx_global, c.py, c.px);
+      }
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+  }
   const bool solve_mode = !cg_mode && (cli.has("tol") || cli.has("rtol"));
   CgOpts co;
   CgResult cr;
@@ -350,7 +503,7 @@ int main(int argc, char** argv) {
     co.norm = nm == "max" ? 1 : 0;
     co.lag = static_cast<int>(cli.geti("lag", 1));
     co.check_every = static_cast<int>(cli.geti("check-every", 0));
-    if (co.check_every == 0) co.check_every = 10;
+    if (co.check_every == 0) co.check_every = mg_mode ? 1 : 10;
     if (c.periodic || (nm != "l2" && nm != "max") || co.lag < 0 || co.lag > 8 || co.check_every < 1 || n_iter < 1 ||
         !(co.tol >= 0) || !(co.rtol >= 0) || !std::isfinite(co.tol) || !std::isfinite(co.rtol)) {
       if (rank == 0)
@@ -367,6 +520,12 @@ int main(int argc, char** argv) {
     ho.lag = co.lag;
     ho.check_every = co.check_every;
     ho.max_iters = co.max_iters;
+    mo.tol = co.tol;
+    mo.rtol = co.rtol;
+    mo.norm = co.norm;
+    mo.lag = co.lag;
+    mo.check_every = co.check_every;
+    mo.max_cycles = co.max_iters;
   }
   const bool cg_fixed = cg_mode && !(co.tol > 0) && !(co.rtol > 0);
   SolveOpts so;
@@ -415,7 +574,25 @@ int main(int argc, char** argv) {
     lnx = solver.nx();
     lny = solver.ny();
     int total_sweeps = n_warmup + n_iter;  // what --check replays
-    if (cheby_mode) {
+    if (mg_mode) {
+      // the warm-up as for --cg below: one check's worth of cycles (first
+      // launches, the level hierarchy), then the field is the initial one again
+      MgOpts w = mo;
+      w.tol = w.rtol = 0;
+      w.max_cycles = w.check_every = mo.check_every;
+      w.lag = 0;
+      solver.mg(w);
+      solver.prepare(1);
+      MPI_Barrier(MPI_COMM_WORLD);
+      const double t0 = wtime();
+      mr = solver.mg(mo);
+      double dt = wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &dt, 1, MPI_DOUBLE, MPI_MAX, MPI_COMM_WORLD);
+      solve_ms = dt * 1e3;
+      t_step = dt / (mr.iters > 0 ? mr.iters : 1);
+      total_sweeps = mr.iters;
+      static_cast<CheckResult&>(cr) = mr;  // reported through --cg's lines
+    } else if (cheby_mode) {
       // the warm-up as for --cg below: one check's worth of iterations (first
       // launches, the halo plans), then the field is the initial one again
       ChebyOpts w;
@@ -494,7 +671,9 @@ int main(int argc, char** argv) {
       if (rank == 0) {
         double umax = 0;
         std::vector<double> ref =
-            cheby_mode ? serial_cheby(c.ny_global, c.nx_global, total_sweeps, rho_used, c.source, c.source_amp,
+            mg_mode ? serial_mg(c.ny_global, c.nx_global, total_sweeps, mo, mr.levels, mr.coarse_iters, mr.coarse_rho,
+                                c.source, c.source_amp, c.seed, c.init, &umax)
+            : cheby_mode ? serial_cheby(c.ny_global, c.nx_global, total_sweeps, rho_used, c.source, c.source_amp,
                                       c.seed, c.init, &umax)
             : cg_mode ? serial_cg(c.ny_global, c.nx_global, total_sweeps, c.source, c.source_amp, c.seed, c.init, &umax)
                     : serial_jacobi(c.ny_global, c.nx_global, total_sweeps, c.periodic, c.periodic_axes, c.source,
@@ -563,29 +742,40 @@ int main(int argc, char** argv) {
         std::printf("source    = %s%s every 1 sweeps (set-up 0 sweeps, %0.3f ms, %0.1f MiB)\n",
                     c.source == 1 ? "poly" : "random", amp, src_setup_ms, src_mib);
     }
+    const char* solver_name = mg_mode ? "multigrid" : (cheby_mode ? "chebyshev" : "cg");
+    const char* unit = mg_mode ? "cycle" : "iteration";
     if (cg_mode) {
-      std::printf("solver    = %s\n", cheby_mode ? "chebyshev" : "cg");
+      std::printf("solver    = %s\n", solver_name);
       if (cheby_mode) std::printf("rho       = %.17g%s\n", rho_used, ho.rho == 0 ? " (closed form)" : "");
+      if (mg_mode) {
+        std::printf("levels    = %d (coarsest %lld x %lld, %d iterations, rho %.6g)\n", mr.levels,
+                    (long long)mr.coarse_ny, (long long)mr.coarse_nx, mr.coarse_iters, mr.coarse_rho);
+        std::printf("cycle     = V(%d,%d), omega %g\n", mo.nu1, mo.nu2, mo.omega);
+      }
       if (cg_fixed)
-        std::printf("solve     = fixed count, %s norm, check every %d iterations\n", co.norm ? "max" : "l2",
-                    co.check_every);
+        std::printf("solve     = fixed count, %s norm, check every %d %ss\n", co.norm ? "max" : "l2",
+                    co.check_every, unit);
       else
-        std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d iterations, lag %d\n", co.tol, co.rtol,
-                    co.norm ? "max" : "l2", co.check_every, co.lag);
+        std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d %ss, lag %d\n", co.tol, co.rtol,
+                    co.norm ? "max" : "l2", co.check_every, unit, co.lag);
       if (co.max_iters != cap_asked)
         std::printf("steps     = at most %d (%d rounded up to a multiple of %d)\n", co.max_iters, cap_asked,
                     co.check_every);
       else
         std::printf("steps     = at most %d\n", co.max_iters);
+      const char* count = mg_mode ? "cycles   " : "iters    ";
       if (cg_fixed) {
-        std::printf("iters     : %d (fixed count, %d checks)\n", cr.iters, cr.checks);
+        std::printf("%s : %d (fixed count, %d checks)\n", count, cr.iters, cr.checks);
       } else {
         std::printf("converged : %s%s\n", cr.converged ? "yes" : "no", cr.failed ? " (non-finite residual)" : "");
-        std::printf("iters     : %d (criterion met at %d, %d checks, lag %d)\n", cr.iters, cr.residual_iters, cr.checks,
+        std::printf("%s : %d (criterion met at %d, %d checks, lag %d)\n", count, cr.iters, cr.residual_iters, cr.checks,
                     co.lag);
       }
       std::printf("TIME solve: %0.6f ms\n", solve_ms);
-      std::printf("TIME iter : %0.6f ms per iteration\n", t_step * 1e3);
+      if (mg_mode)
+        std::printf("TIME cycle: %0.6f ms per cycle\n", t_step * 1e3);
+      else
+        std::printf("TIME iter : %0.6f ms per iteration\n", t_step * 1e3);
     } else if (solve_mode) {
       std::printf("solve     = r <= max(%g, %g * r0), %s norm, check every %d sweeps, lag %d\n", so.tol, so.rtol,
                   so.norm ? "max" : "l2", so.check_every, so.lag);
@@ -609,10 +799,10 @@ int main(int argc, char** argv) {
     if (halo_us > 0)
       std::printf("halo      : %0.2f us per exchange (%zu B, %zu msgs per rank)\n", halo_us, hbytes, hmsgs);
     std::printf("residual  : %.10e\n", resid);
-    if (cg_mode && !cheby_mode)
+    if (cg_mode && !cheby_mode && !mg_mode)
       std::printf("true resid: %.10e (max %.10e)\n", cr.true_residual, cr.true_residual_max);
     if (max_diff >= 0 && cg_mode)
-      std::printf("check     : max|diff| vs serial %s = %.3e (bound %.3e) %s\n", cheby_mode ? "chebyshev" : "cg",
+      std::printf("check     : max|diff| vs serial %s = %.3e (bound %.3e) %s\n", solver_name,
                   max_diff, check_bound,
                   max_diff <= check_bound ? "OK" : "FAIL");
     else if (max_diff >= 0)
@@ -627,13 +817,17 @@ int main(int argc, char** argv) {
     if (solve_mode)
       j.add("converged", sr.converged != 0).add("sweeps", sr.iters).add("residual_sweeps", sr.residual_iters)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
-    if (cg_mode)
+    if (mg_mode)
+      j.add("solver", "multigrid").add("levels", mr.levels).add("cycles", mr.iters)
+          .add("residual_cycles", mr.residual_iters).add("checks", mr.checks).add("converged", mr.converged != 0)
+          .add("solve_ms", solve_ms).add("r0", mr.r0).add("residual_max", mr.residual_max);
+    else if (cg_mode)
       j.add("solver", cheby_mode ? "chebyshev" : "cg").add("converged", cr.converged != 0).add("iters", cr.iters)
           .add("residual_iters", cr.residual_iters).add("checks", cr.checks).add("solve_ms", solve_ms).add("r0", cr.r0)
           .add("residual_max", cr.residual_max);
     if (cheby_mode)
       j.add("rho", rho_used);
-    else if (cg_mode)
+    else if (cg_mode && !mg_mode)
       j.add("true_residual", cr.true_residual);
     if (c.source != 0)
       j.add("source", c.source == 1 ? "poly" : "random").add("src_every", src_every > 0 ? src_every : 1)

@@ -265,6 +265,46 @@ int gmt_engine_jacobi_cheby(void* p, const gmt_engine_cheby_opts* o, gmt_engine_
   return 0;
 }
 double gmt_engine_cheby_rho(int64_t nx_global, int64_t ny_global) { return gmt::cheby_rho(nx_global, ny_global); }
+int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_result* out) {
+  if (!p || !o || !out) return 1;
+  gmt::watchdog_kick("engine: jacobi mg");
+  auto* h = static_cast<Handle*>(p);
+  auto& s = *h->s;
+  if (s.periodic()) return 2;
+  gmt::MgOpts mo;
+  mo.tol = o->tol;
+  mo.rtol = o->rtol;
+  mo.norm = o->norm;
+  mo.max_cycles = o->max_cycles;
+  mo.check_every = o->check_every;
+  mo.lag = o->lag;
+  mo.nu1 = o->nu1;
+  mo.nu2 = o->nu2;
+  mo.omega = o->omega;
+  mo.max_levels = o->max_levels;
+  mo.coarse_iters = o->coarse_iters;
+  gmt::MgResult r;
+  try {
+    r = s.mg(mo);
+  } catch (const std::invalid_argument& e) {
+    const std::string what = e.what();
+    if (what.find("no coarse level") == std::string::npos) return 1;
+    return what.find("must be even") != std::string::npos ? 3 : 4;
+  }
+  *out = {r.converged, r.iters,  r.checks,    r.residual_iters, r.residual,     r.residual_max, r.r0,
+          r.failed,    r.levels, r.coarse_ny, r.coarse_nx,      r.coarse_iters, r.coarse_rho};
+  return 0;
+}
+int gmt_engine_mg_coarse_iters(double rho) { return gmt::mg_coarse_iters(rho); }
+int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels, int64_t* out, int max) {
+  if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || !out) return -1;
+  const auto t = gmt::mg_level_table(ny, nx, py, px, max_levels);
+  for (int i = 0; i < static_cast<int>(t.size()) && i < max; ++i) {
+    out[2 * i] = t[i].first;
+    out[2 * i + 1] = t[i].second;
+  }
+  return static_cast<int>(t.size());
+}
 int gmt_engine_jacobi_periodic(void* p) { return p && static_cast<Handle*>(p)->s->periodic() ? 1 : 0; }
 int gmt_engine_jacobi_exchange(void* p) {
   gmt::watchdog_kick("engine: halo exchange");

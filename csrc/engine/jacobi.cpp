@@ -1331,6 +1331,220 @@ ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
   return res;
 }
 
+// ---- geometric multigrid (gmt/jacobi.hpp MgOpts) ----
+
+int mg_coarse_iters(double rho) {
+  if (!(rho > 0.0)) return 1;
+  const double sigma = (1.0 - std::sqrt(1.0 - rho * rho)) / rho;
+  // volatile: every product is rounded before it is used, as in Python
+  volatile double t = sigma, t2 = 0.0;
+  int k = 1;
+  for (;;) {
+    t2 = t * t;
+    if (2.0 * t / (1.0 + t2) <= 0.1 || k >= 1 << 20) return k;
+    t = t * sigma;
+    ++k;
+  }
+}
+
+std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels) {
+  std::vector<std::pair<int64_t, int64_t>> out{{ny, nx}};
+  // the share boundaries of either axis; a coarser level halves them
+  auto bounds = [](int64_t n, int p) {
+    std::vector<int64_t> b(static_cast<size_t>(p) + 1, n);
+    for (int i = 0; i < p; ++i) {
+      int64_t len = 0;
+      block_split(n, p, i, &b[i], &len);
+    }
+    return b;
+  };
+  auto halve = [](std::vector<int64_t>& b) {
+    for (auto& v : b) v /= 2;
+    for (size_t i = 0; i + 1 < b.size(); ++i)
+      if (b[i + 1] <= b[i]) return false;  // a rank without a coarse row / column
+    return true;
+  };
+  std::vector<int64_t> by = bounds(ny, py), bx = bounds(nx, px);
+  while ((max_levels == 0 || static_cast<int>(out.size()) < max_levels) && ny % 2 == 1 && nx % 2 == 1) {
+    if (!halve(by) || !halve(bx)) break;
+    ny = (ny - 1) / 2;
+    nx = (nx - 1) / 2;
+    out.emplace_back(ny, nx);
+  }
+  return out;
+}
+
+std::unique_ptr<Halo2D> JacobiSolver::ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny,
+                                                int64_t ld, bool corners) {
+  Neighbors nb = nb_;
+  if (!corners) nb.sw = nb.se = nb.nw = nb.ne = -2;
+  Span2D<double> f(field + (yo - 1) * ld + (xo - 1), nx + 2, ny + 2, ld);
+  return std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, corners);
+}
+
+// Every level the problem has (mg_level_table without a limit); a call with
+// max_levels uses the first of them.
+void JacobiSolver::mg_setup() {
+  if (!mg_.empty()) return;
+  watchdog_kick("jacobi: mg set-up");
+  cheby_setup();
+  const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, 0);
+  mg_.resize(table.size());
+  auto zeroed = [&](size_t elems) {
+    Buffer<double> b(elems, GMT_SPACE_DEVICE);
+    GMT_CHECK("memset", gmt_rt_memset_async(b.data(), 0, b.bytes(), s_));
+    return b;
+  };
+  for (size_t l = 0; l < mg_.size(); ++l) {
+    MgLevel& L = mg_[l];
+    L.ny_g = table[l].first;
+    L.nx_g = table[l].second;
+    size_t elems = static_cast<size_t>(ld_) * (ny_ + 2 * g_);
+    if (l == 0) {
+      L.nx = nx_, L.ny = ny_, L.ox = ox_, L.oy = oy_;
+      L.xo = xo_, L.yo = yo_, L.ld = ld_;
+    } else {
+      const MgLevel& P = mg_[l - 1];
+      L.ox = P.ox / 2, L.nx = (P.ox + P.nx) / 2 - L.ox;
+      L.oy = P.oy / 2, L.ny = (P.oy + P.ny) / 2 - L.oy;
+      L.xo = 8, L.yo = 1, L.ld = round_up(L.xo + L.nx + 1, 64);
+      elems = static_cast<size_t>(L.ld) * (L.ny + 2);
+      for (int b = 0; b < 2; ++b) {
+        L.u[b] = zeroed(elems);
+        L.up[b] = L.u[b].data();
+      }
+      L.s = zeroed(elems);
+      L.sp = L.s.data();
+    }
+    if (l + 1 < mg_.size()) L.d = zeroed(elems);
+  }
+  mg_ws_ = Buffer<double>(static_cast<size_t>(gmt_cg_workspace(nx_, ny_)) + 2, GMT_SPACE_DEVICE);
+  GMT_CHECK("mg set-up sync", gmt_rt_stream_synchronize(s_));
+  for (size_t l = 0; l < mg_.size(); ++l) {
+    MgLevel& L = mg_[l];
+    if (l > 0)
+      for (int b = 0; b < 2; ++b) L.hu[b] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true);
+    if (L.d.data()) L.hd = ring_halo(L.d.data(), L.xo, L.yo, L.nx, L.ny, L.ld, true);
+  }
+  watchdog_kick("jacobi: mg ready");
+}
+
+void JacobiSolver::mg_ring(int l) {
+  MgLevel& L = mg_[l];
+  if (L.ring) return;
+  Halo2D& h = l == 0 ? *cheby_halo_[L.cur] : *L.hu[L.cur];
+  if (h.active()) {
+    h.start(s_);
+    h.finish(s_);
+  }
+  L.ring = true;
+}
+
+void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho) {
+  MgLevel& L = mg_[l];
+  const int64_t ldf = L.sp ? L.ld : 0;
+  const double c1 = L.sp ? 1.0 : 0.0;
+  if (l == levels - 1) {
+    // the Chebyshev iteration of cheby() from u = 0 (the caller zeroed it)
+    const double rho2 = coarse_rho * coarse_rho;
+    double w = 1.0;
+    for (int k = 0; k < coarse_iters; ++k) {
+      mg_ring(l);
+      if (k == 0) {
+        GMT_CHECK("mg coarse sweep", gmt_jacobi5(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.up[L.cur ^ 1], L.ld, L.sp, ldf,
+                                                 kC0, c1, nullptr, s_));
+      } else {
+        w = cheby_next_weight(rho2, w, k);
+        GMT_CHECK("mg coarse step", gmt_cheby_step(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, w,
+                                                   L.up[L.cur ^ 1], L.ld, s_));
+      }
+      L.cur ^= 1;
+      L.ring = false;
+    }
+    return;
+  }
+  auto smooth = [&](int n) {
+    for (int i = 0; i < n; ++i) {
+      mg_ring(l);
+      GMT_CHECK("mg smooth", gmt_mg_smooth(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, o.omega,
+                                           L.up[L.cur ^ 1], L.ld, s_));
+      L.cur ^= 1;
+      L.ring = false;
+    }
+  };
+  MgLevel& C = mg_[l + 1];
+  const int px = L.ox % 2 == 0 ? 1 : 0, py = L.oy % 2 == 0 ? 1 : 0;
+  smooth(o.nu1);
+  mg_ring(l);
+  GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, L.d.data(),
+                                        L.ld, mg_ws_.data(), mg_ws_.data() + 2, s_));
+  if (L.hd->active()) {
+    L.hd->start(s_);
+    L.hd->finish(s_);
+  }
+  GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
+                                           C.yo, C.ld, s_));
+  // u = 0 on the coarser level, ring included: current on every rank
+  GMT_CHECK("memset", gmt_rt_memset_async(C.up[0], 0, C.u[0].bytes(), s_));
+  C.cur = 0;
+  C.ring = true;
+  mg_cycle(l + 1, levels, o, coarse_iters, coarse_rho);
+  Halo2D& hc = *C.hu[C.cur];
+  if (hc.active()) {
+    hc.start(s_);
+    hc.finish(s_);
+  }
+  C.ring = true;
+  GMT_CHECK("mg prolong", gmt_mg_prolong_add(L.xo, L.nx, L.yo, L.ny, px, py, C.up[C.cur], C.xo, C.yo, C.ld,
+                                             L.up[L.cur], L.ld, s_));
+  L.ring = false;
+  smooth(o.nu2);
+}
+
+MgResult JacobiSolver::mg(const MgOpts& o) {
+  const CheckLoop loop{"mg", "max_cycles", "jacobi mg check", o.tol, o.rtol, o.norm, o.max_cycles,
+                       o.check_every == 0 ? 1 : o.check_every, o.lag, false};
+  loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
+                    o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0,
+                ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0");
+  if (periodic())
+    throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
+  const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels);
+  if (table.size() < 2)
+    throw std::invalid_argument(
+        std::string("JacobiSolver::mg: no coarse level: ") +
+        (cfg_.ny_global % 2 == 0 || cfg_.nx_global % 2 == 0 ? "nx + 1 and ny + 1 must be even"
+                                                            : "a rank of the process grid would own no coarse point"));
+  mg_setup();
+  const int levels = static_cast<int>(table.size());
+  MgResult res;
+  res.levels = levels;
+  res.coarse_ny = table.back().first;
+  res.coarse_nx = table.back().second;
+  res.coarse_rho = cheby_rho(res.coarse_nx, res.coarse_ny);
+  res.coarse_iters = o.coarse_iters > 0 ? o.coarse_iters : mg_coarse_iters(res.coarse_rho);
+  MgLevel& F = mg_[0];
+  for (int b = 0; b < 2; ++b) F.up[b] = buf_[b].data();
+  F.sp = src_f();
+  F.cur = parity_;
+  F.ring = fresh_[parity_];
+  run_checks(loop, res,
+             [&] {
+               for (int j = 0; j < loop.every; ++j) mg_cycle(0, levels, o, res.coarse_iters, res.coarse_rho);
+               fresh_[0] = fresh_[1] = false;  // at most the faces of one buffer are current
+               parity_ = F.cur;
+               advanced_ = true;
+               watchdog_kick("jacobi mg cycles enqueued");
+             },
+             [&](int) {
+               mg_ring(0);
+               enqueue_residual(true);
+               return rn_dev_.data();
+             });
+  synchronize();
+  return res;
+}
+
 void JacobiSolver::exchange_only() {
   Halo2D& h = *halo_[parity_];
   // the exchange packs the current field and writes its ghost ring: order it

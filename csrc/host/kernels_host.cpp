@@ -436,6 +436,84 @@ int gmt_cheby_step(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double*
   return 0;
 }
 
+// the multigrid kernels (csrc/kernels/mg.hip): the same checks, codes and cell
+// expressions (this file is built with -ffp-contract=off)
+int gmt_mg_smooth_path(int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*,
+                       int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+int gmt_mg_restrict_path(int64_t, int64_t, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+int gmt_mg_prolong_add_path(int64_t, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+
+int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld, const double* f,
+                  int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo, void*) {
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (!u || !out || x0 < 1 || y0 < 1 || ld < x0 + nx + 1 || ldo < x0 + nx || (f && ldf < x0 + nx)) return 1;
+  for (int64_t y = y0; y < y0 + ny; ++y)
+    for (int64_t x = x0; x < x0 + nx; ++x) {
+      const double* c = u + y * ld + x;
+      double o = c0 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+      if (f) o = o + c1 * f[y * ldf + x];
+      const double t = o - c[0];
+      const double wt = omega * t;
+      out[y * ldo + x] = c[0] + wt;
+    }
+  return 0;
+}
+
+int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* d, int64_t ldd,
+                    double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void*) {
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (!d || !sc || x0 < 1 || y0 < 1 || cx0 < 0 || cy0 < 0 || ldd < x0 + nx + 1 || ldc < cx0 + mx) return 1;
+  auto h = [](const double* p) {
+    const double t = 2.0 * p[0];
+    return (p[-1] + p[1]) + t;
+  };
+  for (int64_t J = 0; J < my; ++J)
+    for (int64_t I = 0; I < mx; ++I) {
+      const double* p = d + (y0 + py + 2 * J) * ldd + x0 + px + 2 * I;
+      const double hs = h(p - ldd), hc = h(p), hn = h(p + ldd);
+      const double t = 2.0 * hc;
+      sc[(cy0 + J) * ldc + cx0 + I] = cs * ((hs + hn) + t);
+    }
+  return 0;
+}
+
+int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* e, int64_t cx0,
+                       int64_t cy0, int64_t lde, double* u, int64_t ld, void*) {
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
+  const int64_t mx = (nx - px + 1) / 2;
+  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < 1 || cy0 < 1 || lde < cx0 + mx + 1 || ld < x0 + nx) return 1;
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) {
+      const int64_t di = i - px, dj = j - py;  // >= -1
+      const bool onx = (di & 1) == 0, ony = (dj & 1) == 0;
+      // the coarse column / row the cell sits on, else the one west / south of it (-1: the ring)
+      const int64_t I = onx ? di / 2 : (di + 1) / 2 - 1;
+      const int64_t J = ony ? dj / 2 : (dj + 1) / 2 - 1;
+      const double* p = e + (cy0 + J) * lde + cx0 + I;
+      double* q = u + (y0 + j) * ld + x0 + i;
+      double t;
+      if (onx && ony)
+        t = p[0];
+      else if (ony)
+        t = 0.5 * (p[0] + p[1]);
+      else if (onx)
+        t = 0.5 * (p[0] + p[lde]);
+      else
+        t = 0.25 * ((p[0] + p[1]) + (p[lde] + p[lde + 1]));
+      *q = *q + t;
+    }
+  return 0;
+}
+
 int gmt_jacobi5_rects(int n_rect, const int64_t* r, const double* u, double* un, int64_t ld,
                       const double* f, int64_t ldf, double c0, double c1, void*) {
   if (n_rect > 4) return 1;

@@ -122,6 +122,39 @@ typedef struct gmt_engine_cheby_result {
 int gmt_engine_jacobi_cheby(void* h, const gmt_engine_cheby_opts* opts, gmt_engine_cheby_result* out);
 /* the closed-form spectral radius of an nx x ny global interior */
 double gmt_engine_cheby_rho(int64_t nx_global, int64_t ny_global);
+/* Geometric multigrid V-cycles from the current field (JacobiSolver::mg,
+ * gmt/jacobi.hpp MgOpts / MgResult): an iteration is one cycle, cg's
+ * criterion, lagged check and fixed-count mode. */
+typedef struct gmt_engine_mg_opts {
+  double tol, rtol;
+  int norm;         /* 0 L2, 1 max */
+  int max_cycles;   /* a positive multiple of check_every */
+  int check_every;  /* 0 = 1 */
+  int lag;          /* 0..8 */
+  int nu1, nu2;     /* damped Jacobi sweeps before / after the correction, nu1 + nu2 > 0 */
+  double omega;     /* in (0, 1] */
+  int max_levels;   /* 0 = no limit, else >= 2 */
+  int coarse_iters; /* 0 = gmt_engine_mg_coarse_iters(rho of the coarsest level) */
+} gmt_engine_mg_opts;
+typedef struct gmt_engine_mg_result {
+  int converged, iters, checks, residual_iters;
+  double residual, residual_max, r0;
+  int failed; /* 1: a non-finite residual stopped the iteration */
+  int levels;
+  int64_t coarse_ny, coarse_nx; /* global extents of the coarsest level */
+  int coarse_iters;
+  double coarse_rho;
+} gmt_engine_mg_result;
+/* 0; 1 on invalid options, 2 on an engine with a periodic axis, 3 when the
+ * problem has no coarse level: nx + 1 or ny + 1 odd, 4 when a rank of the
+ * process grid would own no coarse point (nothing enqueued in any of these).
+ * Collective. */
+int gmt_engine_jacobi_mg(void* h, const gmt_engine_mg_opts* opts, gmt_engine_mg_result* out);
+/* the default Chebyshev iteration count on a coarsest level of spectral radius rho */
+int gmt_engine_mg_coarse_iters(double rho);
+/* global {ny, nx} of every level of an ny x nx problem on a py x px grid into
+ * out[2 * max] (level 0 first); returns the number of levels */
+int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels, int64_t* out, int max);
 /* 1 when the engine has a periodic axis */
 int gmt_engine_jacobi_periodic(void* h);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,

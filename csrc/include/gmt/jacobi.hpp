@@ -37,6 +37,7 @@
 
 #include <functional>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "gmt/buffer.hpp"
@@ -188,6 +189,50 @@ double cheby_rho(int64_t nx_global, int64_t ny_global);
 // the weights are bit for bit Python's given the same rho
 double cheby_next_weight(double rho2, double w, int k);
 
+// JacobiSolver::mg: geometric multigrid V-cycles on (I - J) u = b.  Levels are
+// vertex-centred: a level with global interior ny x nx has the coarser level
+// (ny-1)/2 x (nx-1)/2, coarse point (J, I) on fine interior point (2J+1, 2I+1);
+// a rank that owns fine columns [ox, ox+nx) owns coarse columns
+// [ox/2, (ox+nx)/2), rows alike (mg_level_table).  One cycle on a level:
+//   coarsest: u = 0, coarse_iters Chebyshev iterations (the first the plain
+//             sweep, weights of cheby_next_weight, rho = cheby_rho of the level);
+//   else:     nu1 damped Jacobi sweeps u' = u + omega*(G(u) - u), each after a
+//             1-wide faces-only exchange; d = G(u) - u; the ring of d exchanged
+//             with corners; s_coarse = full weighting of d (weights summing to
+//             4: the coarse levels run the same operator, c0 = 0.25, c1 = 1);
+//             u_coarse = 0; the cycle on the coarser level; the ring of
+//             u_coarse exchanged with corners; u += bilinear interpolation of
+//             u_coarse; nu2 sweeps.
+// The fine ring is the real Dirichlet ring, coarse rings are zero.  An
+// iteration is one cycle; criterion and lagged check are solve()'s.
+struct MgOpts {
+  double tol = 0.0, rtol = 0.0;  // both 0: fixed-count mode, exactly max_cycles cycles
+  int norm = 0;                  // 0: L2, 1: max |d|
+  int max_cycles = 0;            // the cap: a positive multiple of check_every
+  int check_every = 0;           // cycles between two checks (0 = 1)
+  int lag = 1;                   // the host decides on check i - lag after enqueuing check i (0..8)
+  int nu1 = 2, nu2 = 2;          // sweeps before / after the coarse-level correction
+  double omega = 0.8;            // the damping, in (0, 1]
+  int max_levels = 0;            // 0: as many as the extents and the process grid allow; else >= 2
+  int coarse_iters = 0;          // Chebyshev iterations on the coarsest level (0 = mg_coarse_iters(rho))
+};
+struct MgResult : CheckResult {
+  int levels = 0;                          // levels used, the fine one included
+  int64_t coarse_ny = 0, coarse_nx = 0;    // global extents of the coarsest
+  int coarse_iters = 0;                    // Chebyshev iterations on it
+  double coarse_rho = 0.0;                 // and their spectral radius
+};
+// The default coarse_iters: with sigma = (1 - sqrt(1 - rho^2))/rho and t = sigma,
+// the smallest k >= 1 with 2t/(1 + t^2) <= 0.1, t multiplied by sigma each
+// time k grows by one; 1 for rho = 0.
+int mg_coarse_iters(double rho);
+// Global extents {ny, nx} of every level, the fine one first: coarsening goes
+// on while nx + 1 and ny + 1 are even, every rank of the py x px grid keeps at
+// least one coarse row and column, and max_levels (0: no limit) is not
+// reached.  A function of the global extents and block_split only: every rank
+// computes the same table.
+std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels);
+
 class JacobiSolver {
  public:
   JacobiSolver(comm::Transport& t, const JacobiConfig& c);
@@ -242,6 +287,17 @@ class JacobiSolver {
   // std::invalid_argument on bad options or an engine with a periodic axis
   // (rho = 1, the fixed point is not unique); nothing is enqueued then.
   ChebyResult cheby(const ChebyOpts& o);
+  // Multigrid V-cycles from the current field (MgOpts above).  The solution
+  // replaces the current field and the parity flips as in step() (with an odd
+  // nu1 + nu2); run(k) afterwards keeps sweeping from it and captured graphs
+  // stay valid.  A source enters as the fine level's f.  Every cell's
+  // arithmetic is independent of the decomposition: the field is bitwise the
+  // same on every process grid.  The first call builds the level hierarchy
+  // (coarse fields, one fine field, halo plans: collective).  Throws
+  // std::invalid_argument, nothing enqueued, on bad options, an engine with a
+  // periodic axis, or a problem with no coarse level (nx + 1 or ny + 1 odd, or
+  // a rank that would own no coarse point).
+  MgResult mg(const MgOpts& o);
   // one blocking halo exchange of the current field (latency measurements);
   // ordered after every pass already enqueued
   void exchange_only();
@@ -356,6 +412,12 @@ class JacobiSolver {
                   const std::function<const double*(int)>& check);
   void cg_setup();          // the state of cg() (first use; collective)
   void cheby_setup();       // the halo plans of cheby() (first use; collective)
+  // the 1-wide ring of a field with corners, or its faces only (collective)
+  std::unique_ptr<Halo2D> ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny, int64_t ld,
+                                    bool corners);
+  void mg_setup();          // the levels of mg() (first use; collective)
+  void mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho);
+  void mg_ring(int l);      // the faces of level l's current buffer hold the neighbours' current values
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
   void push_block(int parity, int k);  // one inline-halo pass + its hand-over
   void push_pass(int parity, int k);   // the pass launch alone
@@ -403,6 +465,22 @@ class JacobiSolver {
   std::unique_ptr<Halo2D> cg_halo_;
   // cheby(): the 1-wide ring of either buffer's interior (faces only)
   std::unique_ptr<Halo2D> cheby_halo_[2];
+  // mg(): level 0 is buf_ and f_ with cheby_halo_ (u, s and the pair of halo
+  // plans below stay empty there); coarser levels own their fields in buf_'s
+  // layout (interior origin x = 8, y = 1, pitch padded to 64, a zero ring)
+  struct MgLevel {
+    int64_t ny_g = 0, nx_g = 0;                        // global interior
+    int64_t nx = 0, ny = 0, ox = 0, oy = 0;            // this rank's share and its global offset
+    int64_t xo = 8, yo = 1, ld = 0;                    // interior origin, pitch
+    Buffer<double> u[2], s, d;                         // d: the residual (none on the last level)
+    double* up[2] = {nullptr, nullptr};                // the level's buffer pair
+    const double* sp = nullptr;                        // its source (level 0: NULL without one)
+    int cur = 0;                                       // up[cur] is the level's current field
+    bool ring = false;                                 // its faces are current
+    std::unique_ptr<Halo2D> hu[2], hd;                 // rings with corners of u[0], u[1] and d
+  };
+  std::vector<MgLevel> mg_;
+  Buffer<double> mg_ws_;  // gmt_cg_apply's workspace and its two results (level 0's size)
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values
   gmt_stream_t s_ = nullptr, cs_ = nullptr;

@@ -286,6 +286,59 @@ int gmt_cheby_step(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double*
 int gmt_cheby_step_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f,
                         int64_t ldf, const double* v, int64_t ldv, int64_t* seg_rows);
 
+/* ---- Geometric multigrid over the Laplace sweep (csrc/kernels/mg.hip): the
+ *      smoother and the two grid transfers of a V-cycle of JacobiSolver::mg.
+ *      Levels are vertex-centred: coarse point (J, I) sits on fine interior
+ *      point (2J+1, 2I+1) of the global lattice.  Conventions of
+ *      gmt_cheby_step: absolute x0 >= 1, y0 >= 1, every field with its own
+ *      pitch, asynchronous on `stream`, every cell evaluated without
+ *      contraction in exactly the order given, on both backends, so the fields
+ *      are bitwise NumPy's.  An empty region (nx or ny 0) launches nothing and
+ *      returns 0.  Refused (non-zero, the same on both backends): a NULL field,
+ *      a negative extent, x0 < 1 or y0 < 1, a short pitch, px or py outside
+ *      0..1.  No cell outside the output region is written.
+ *
+ * smooth: out = u + omega*(G(u) - u), damped Jacobi, in the order
+ *   o = c0*((W+E)+(N+S)); o = o + c1*f (only with f); t = o - u; out = u + omega*t.
+ *   u and out must not overlap; ld >= x0 + nx + 1, ldo and ldf >= x0 + nx; u
+ *   is read on the region's plus-shaped set.  The row walk with a 16-B store:
+ *   16 B per point, 24 with f. */
+int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld, const double* f,
+                  int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo, void* stream);
+/* restrict: full weighting of the fine field d over the fine region nx x ny at
+ *   (x0, y0) into the coarse field sc at (cx0, cy0).  px, py in {0, 1}: the
+ *   region-relative fine index of the first coarse column / row (1 when the
+ *   region's global offset is even, 0 when it is odd); mx = (nx - px + 1)/2 by
+ *   my = (ny - py + 1)/2 coarse cells are written.  With the centre
+ *   (x, y) = (x0+px+2I, y0+py+2J) and H(r) = (d[r][x-1] + d[r][x+1]) + 2*d[r][x]:
+ *   sc[cy0+J][cx0+I] = cs*((H(y-1) + H(y+1)) + 2*H(y)).  The weights sum to
+ *   16 cs (the engine's cs = 0.25 folds in the factor 4 between h^2 and (2h)^2).
+ *   d is read on the region and its 1-wide ring, corners included;
+ *   ldd >= x0 + nx + 1, ldc >= cx0 + mx, cx0 and cy0 >= 0. */
+int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* d, int64_t ldd,
+                    double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void* stream);
+/* prolong_add: u += P e on the fine region, P bilinear interpolation from the
+ *   coarse field e whose cell (0, 0) of the region's mx x my is at (cx0, cy0);
+ *   px, py as for restrict.  By how a fine cell sits relative to the coarse
+ *   points: on one, u + e; between two in x, u + 0.5*(eW + eE); between two in
+ *   y, u + 0.5*(eS + eN); between four, u + 0.25*((eSW + eSE) + (eNW + eNE))
+ *   (S the lower row index).  e is read on its mx x my cells and their 1-wide
+ *   ring, corners included; cx0 and cy0 >= 1, lde >= cx0 + mx + 1,
+ *   ld >= x0 + nx.  e and u must not overlap. */
+int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* e, int64_t cx0,
+                       int64_t cy0, int64_t lde, double* u, int64_t ld, void* stream);
+/* The kernel each call would launch, nothing launched.  smooth:
+ * GMT_PATH_ROW_WALK (x0 even, every pointer 16-B aligned, every pitch even;
+ * *seg_rows, may be NULL, = rows per segment) or GMT_PATH_SCALAR (*seg_rows =
+ * 0); f counts only when non-NULL.  restrict / prolong_add: GMT_PATH_PT (pairs
+ * of coarse cells / of fine cells per lane under the same rule, for restrict
+ * with an even cx0 too; an odd count keeps it with a scalar last column) or
+ * GMT_PATH_SCALAR.  GMT_PATH_NONE on the CPU backend. */
+int gmt_mg_smooth_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f, int64_t ldf,
+                       const double* out, int64_t ldo, int64_t* seg_rows);
+int gmt_mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc);
+int gmt_mg_prolong_add_path(int64_t x0, const double* e, int64_t lde, const double* u, int64_t ld);
+
 /* ---- Temporal-blocking Jacobi (csrc/kernels/jacobi5tb.hip): `sweeps` fused
  *      Laplace sweeps per memory pass, un = J^sweeps(u), on up to 8 output
  *      rects {x0, nx, y0, ny} (absolute array coordinates, x0 >= sweeps,

@@ -1,5 +1,6 @@
 // The row walk shared by the read-only residual (jacobi5_resid.hip), CG's
-// operator apply (cg.hip) and the Chebyshev step (cheby.hip): one pass over
+// operator apply (cg.hip), the Chebyshev step (cheby.hip) and the multigrid
+// smoother (mg.hip): one pass over
 // the 5-point neighbourhood of u that loads every row once per segment.
 //
 // A workgroup is four waves side by side (512 columns) on one row segment;

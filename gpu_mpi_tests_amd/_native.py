@@ -173,6 +173,21 @@ _SIGS = {
         [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
     ),
     "gmt_cheby_step_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_mg_smooth": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
+    ),
+    "gmt_mg_smooth_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_mg_restrict": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_dbl, c_vp, c_i64, c_i64, c_i64, c_vp],
+    ),
+    "gmt_mg_restrict_path": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "gmt_mg_prolong_add": (
+        c_int,
+        [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
+    ),
+    "gmt_mg_prolong_add_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
     "gmt_jacobi5_rects": (
         c_int,
         [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp],

@@ -97,6 +97,23 @@ class ChebyResult(ctypes.Structure):
                 ("failed", ctypes.c_int)]
 
 
+class MgOpts(ctypes.Structure):
+    """gmt_engine_mg_opts (csrc/include/gmt/engine.h)."""
+    _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
+                ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
+                ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
+                ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int)]
+
+
+class MgResult(ctypes.Structure):
+    """gmt_engine_mg_result (csrc/include/gmt/engine.h)."""
+    _fields_ = [("converged", ctypes.c_int), ("iters", ctypes.c_int), ("checks", ctypes.c_int),
+                ("residual_iters", ctypes.c_int), ("residual", ctypes.c_double),
+                ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("failed", ctypes.c_int),
+                ("levels", ctypes.c_int), ("coarse_ny", ctypes.c_int64), ("coarse_nx", ctypes.c_int64),
+                ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double)]
+
+
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
 CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
@@ -153,6 +170,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_cg.restype = c_int
     lib.gmt_engine_jacobi_cheby.argtypes = [vp, ctypes.POINTER(ChebyOpts), ctypes.POINTER(ChebyResult)]
     lib.gmt_engine_jacobi_cheby.restype = c_int
+    lib.gmt_engine_jacobi_mg.argtypes = [vp, ctypes.POINTER(MgOpts), ctypes.POINTER(MgResult)]
+    lib.gmt_engine_jacobi_mg.restype = c_int
     lib.gmt_engine_jacobi_periodic.argtypes = [vp]
     lib.gmt_engine_jacobi_periodic.restype = c_int
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
@@ -665,6 +684,58 @@ class NativeJacobi:
             raise ValueError("gmt_engine_jacobi_cheby rejected its options")
         return {n: getattr(r, n) for n, _ in ChebyResult._fields_}
 
+    def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
+           lag: int = 1, nu: tuple = (2, 2), omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0) -> dict:
+        """Geometric multigrid V-cycles from the current field
+        (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
+        ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
+        the coarse-level correction, full weighting, bilinear interpolation,
+        ``coarse_iters`` Chebyshev iterations from zero on the coarsest level
+        (0 = :func:`mg_coarse_iters` of its spectral radius).  Levels are those
+        of :func:`mg_levels` (``max_levels`` 0 = all of them, else >= 2).  An
+        iteration is one cycle; criterion, ``check_every`` (0 = 1), ``lag`` and
+        the fixed-count mode are :meth:`cg`'s.  The solution replaces the
+        current field (the parity flips with an odd ``nu[0] + nu[1]``);
+        :meth:`run` afterwards keeps sweeping from it.  The field is bitwise
+        the same on every process grid.  Returns the fields of MgResult:
+        ``converged``, ``iters`` (cycles), ``checks``, ``residual_iters``,
+        ``residual``, ``residual_max``, ``r0``, ``failed``, ``levels``,
+        ``coarse_ny``, ``coarse_nx``, ``coarse_iters``, ``coarse_rho``.
+        Identical on every rank.  ValueError on bad options, a periodic axis,
+        or a problem with no coarse level (``nx + 1`` or ``ny + 1`` odd, or a
+        rank that would own no coarse point).  Collective."""
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
+        every = int(check_every) if check_every else 1
+        if isinstance(lag, bool) or not 0 <= int(lag) <= MAX_LAG:
+            raise ValueError(f"lag must be 0..{MAX_LAG}, got {lag!r}")
+        if every < 1:
+            raise ValueError(f"check_every must be >= 1 (0 = 1), got {check_every!r}")
+        if int(max_cycles) < 1 or int(max_cycles) % every:
+            raise ValueError(f"max_cycles must be a positive multiple of check_every ({every}), got {max_cycles!r}")
+        tol, rtol, omega = float(tol), float(rtol), float(omega)
+        if not (np.isfinite(tol) and np.isfinite(rtol)) or tol < 0 or rtol < 0:
+            raise ValueError("tol and rtol must be finite and >= 0")
+        nu1, nu2 = (int(v) for v in nu)
+        if nu1 < 0 or nu2 < 0 or nu1 + nu2 == 0:
+            raise ValueError(f"nu must be two counts >= 0 with a positive sum, got {nu!r}")
+        if not 0.0 < omega <= 1.0:
+            raise ValueError(f"omega must be in (0, 1], got {omega!r}")
+        if int(max_levels) < 0 or int(max_levels) == 1 or int(coarse_iters) < 0:
+            raise ValueError("max_levels must be 0 or >= 2 and coarse_iters >= 0")
+        o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
+                   nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters))
+        r = MgResult()
+        rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
+        if rc == 2:
+            raise ValueError("mg needs Dirichlet sides: I - J is singular on a periodic axis")
+        if rc in (3, 4):
+            raise ValueError("mg: no coarse level: " + ("nx + 1 and ny + 1 must be even" if rc == 3 else
+                                                        "a rank of the process grid would own no coarse point"))
+        if rc:
+            raise ValueError("gmt_engine_jacobi_mg rejected its options")
+        return {n: getattr(r, n) for n, _ in MgResult._fields_}
+
     def interior(self) -> np.ndarray:
         out = np.empty((self.ny, self.nx), dtype=np.float64)
         self.lib.gmt_engine_jacobi_copy_interior(self.h, out.ctypes.data)
@@ -979,3 +1050,124 @@ def serial_cheby(ny: int, nx: int, iters: int, rho: float, init: str = "analytic
         if resid_every and (it + 1) % resid_every == 0:
             series[it + 1] = resid(u)
     return (u[1:-1, 1:-1].copy() if keep is None else kept), series
+
+
+def mg_coarse_iters(rho: float) -> int:
+    """The default Chebyshev iteration count of :meth:`NativeJacobi.mg` on a
+    coarsest level of spectral radius ``rho`` (the engine's loop, operation for
+    operation): with ``sigma = (1 - sqrt(1 - rho^2))/rho`` and ``t = sigma``,
+    the smallest ``k >= 1`` with ``2t/(1 + t^2) <= 0.1``, ``t`` multiplied by
+    ``sigma`` each time ``k`` grows by one; 1 for ``rho = 0``."""
+    if not rho > 0.0:
+        return 1
+    sigma = (1.0 - math.sqrt(1.0 - rho * rho)) / rho
+    t, k = sigma, 1
+    while not (2.0 * t / (1.0 + t * t) <= 0.1 or k >= 1 << 20):
+        t = t * sigma
+        k += 1
+    return k
+
+
+def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0) -> list:
+    """The level table of :meth:`NativeJacobi.mg`: global ``(ny, nx)`` of every
+    level, the fine one first.  A level has the coarser level
+    ``((ny-1)/2, (nx-1)/2)`` while ``nx + 1`` and ``ny + 1`` are even, every
+    rank of the ``dims = (py, px)`` grid keeps a coarse row and column (a rank
+    owning fine columns ``[ox, ox+nx)`` owns coarse columns
+    ``[ox/2, (ox+nx)/2)``) and ``max_levels`` (0: no limit) is not reached."""
+    def bounds(n, p):
+        base, rem = divmod(n, p)
+        return [i * base + min(i, rem) for i in range(p)] + [n]
+
+    by, bx = bounds(ny, int(dims[0])), bounds(nx, int(dims[1]))
+    out = [(ny, nx)]
+    while (max_levels == 0 or len(out) < max_levels) and ny % 2 == 1 and nx % 2 == 1:
+        by, bx = [b // 2 for b in by], [b // 2 for b in bx]
+        if any(b1 <= b0 for b in (by, bx) for b0, b1 in zip(b, b[1:])):
+            break
+        ny, nx = (ny - 1) // 2, (nx - 1) // 2
+        out.append((ny, nx))
+    return out
+
+
+def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int = 0,
+              source: "str | np.ndarray | None" = None, source_amp: float = 1.0, nu: tuple = (2, 2),
+              omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0, coarse_rho: "float | None" = None,
+              keep=None, start: "np.ndarray | None" = None):
+    """NumPy definition of :meth:`NativeJacobi.mg` on the whole Dirichlet
+    problem: ``cycles`` V-cycles from the engine's initial field, every cell in
+    the kernels' operation order (ops/reference.py ``mg_smooth``,
+    ``mg_restrict``, ``mg_prolong_add``; the coarsest level as
+    :func:`serial_cheby` from zero) — bitwise the engine's field.
+    ``coarse_rho``: the coarsest level's spectral radius (default
+    :func:`cheby_rho`; the engine reports the value it used).  ``start``: an
+    ny x nx interior to start from inside the initial field's ring, as a call
+    on an engine that has already advanced does.  Returns
+    ``(field, series)``: the ny x nx interior after the last cycle — or, with
+    ``keep`` (cycle counts), the dict ``{k: interior after k cycles}`` — and the
+    list of ``(L2, max)`` of the residual ``G(u) - u`` by ``math.fsum``, entry k
+    after k cycles."""
+    from .ops import reference as ref
+
+    levels = mg_levels(ny, nx, (1, 1), max_levels)
+    if len(levels) < 2:
+        raise ValueError("mg: no coarse level: nx + 1 and ny + 1 must be even")
+    nu1, nu2 = (int(v) for v in nu)
+    rho = cheby_rho(*levels[-1]) if coarse_rho is None else float(coarse_rho)
+    citers = int(coarse_iters) or mg_coarse_iters(rho)
+    weights = cheby_weights(rho, citers)
+    u0 = initial_field(ny, nx, init, seed)
+    if start is not None:
+        u0[1:-1, 1:-1] = start
+    U = [[u0, u0.copy()]] + [[np.zeros((m + 2, n + 2)), np.zeros((m + 2, n + 2))] for m, n in levels[1:]]
+    S = [None] + [np.zeros((m + 2, n + 2)) for m, n in levels[1:]]
+    D = [np.zeros((m + 2, n + 2)) for m, n in levels]
+    if source is not None:
+        S[0] = np.zeros((ny + 2, nx + 2))
+        S[0][1:-1, 1:-1] = source_field(ny, nx, source, seed, source_amp)
+
+    def sweep(a, f):
+        o = 0.25 * ((a[1:-1, :-2] + a[1:-1, 2:]) + (a[:-2, 1:-1] + a[2:, 1:-1]))
+        return o if f is None else o + 1.0 * f[1:-1, 1:-1]
+
+    def cycle(lv, cur):
+        """One cycle on level lv from U[lv][cur]; returns the buffer that holds the result."""
+        (m, n), u, f = levels[lv], U[lv], S[lv]
+        if lv == len(levels) - 1:
+            for k in range(citers):
+                a, b = u[cur], u[cur ^ 1]
+                if k == 0:
+                    b[1:-1, 1:-1] = sweep(a, f)
+                else:
+                    pv = b[1:-1, 1:-1]
+                    t = sweep(a, f) - pv
+                    b[1:-1, 1:-1] = pv + weights[k] * t
+                cur ^= 1
+            return cur
+        for _ in range(nu1):
+            ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
+            cur ^= 1
+        a = u[cur]
+        D[lv][1:-1, 1:-1] = sweep(a, f) - a[1:-1, 1:-1]
+        ref.mg_restrict(D[lv], S[lv + 1], 0.25, 1, n, 1, m, 1, 1, 1, 1)
+        U[lv + 1][0][...] = 0.0
+        c = cycle(lv + 1, 0)
+        ref.mg_prolong_add(U[lv + 1][c], a, 1, n, 1, m, 1, 1, 1, 1)
+        for _ in range(nu2):
+            ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
+            cur ^= 1
+        return cur
+
+    def resid(a):
+        d = sweep(a, S[0]) - a[1:-1, 1:-1]
+        return math.sqrt(math.fsum((d * d).ravel().tolist())), float(np.abs(d).max())
+
+    cur = 0
+    kept = {0: U[0][0][1:-1, 1:-1].copy()} if keep is not None and 0 in keep else {}
+    series = [resid(U[0][0])]
+    for it in range(cycles):
+        cur = cycle(0, cur)
+        series.append(resid(U[0][cur]))
+        if keep is not None and it + 1 in keep:
+            kept[it + 1] = U[0][cur][1:-1, 1:-1].copy()
+    return (U[0][cur][1:-1, 1:-1].copy() if keep is None else kept), series

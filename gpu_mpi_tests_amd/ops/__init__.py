@@ -6,8 +6,9 @@ K4/K5/K11 ``stencil5_2d`` (and its ``stencil5_2d_edges`` /
 K9 ``sum_axis``; K10/K12 ``diff_sq``/``diff_norm``; analytic ``fill_poly``;
 and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
 its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
-``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``
-and ``jacobi5tb`` (K fused sweeps per memory pass).
+``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``,
+the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
+``mg_prolong_add`` and ``jacobi5tb`` (K fused sweeps per memory pass).
 """
 from .kernels import (  # noqa: F401
     abs_max,
@@ -39,6 +40,12 @@ from .kernels import (  # noqa: F401
     jacobi5_rects,
     jacobi5_resid,
     jacobi5_resid_path,
+    mg_prolong_add,
+    mg_prolong_add_path,
+    mg_restrict,
+    mg_restrict_path,
+    mg_smooth,
+    mg_smooth_path,
     jacobi5xk,
     jacobi5tb,
     jacobi5tb_plan,

@@ -575,6 +575,95 @@ def cheby_step_path(u: torch.Tensor, v: torch.Tensor, region: tuple[int, int, in
     return int(path), int(seg.value)
 
 
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    (aa, ab), (ba, bb) = _storage_span(a), _storage_span(b)
+    return aa < bb and ba < ab
+
+
+def mg_smooth(u: torch.Tensor, out: torch.Tensor, omega: float, region: tuple[int, int, int, int],
+              f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 1.0) -> torch.Tensor:
+    """One damped Jacobi sweep of the multigrid cycle over
+    ``region = (x0, nx, y0, ny)`` (gmt_mg_smooth):
+    ``out = u + omega*(G(u) - u)``, ``G(u) = c0*((W + E) + (N + S)) [+ c1*f]``.
+    No contraction: ``out`` is bitwise NumPy's (:func:`reference.mg_smooth`).
+    ``u`` and ``out`` must not share storage.  Returns ``out``."""
+    _check2d(u, "mg_smooth.u")
+    _check2d(out, "mg_smooth.out")
+    if f is not None:
+        _check2d(f, "mg_smooth.f")
+    if _overlap(u, out):
+        raise ValueError("mg_smooth: u and out must not share storage")
+    x0, nx, y0, ny = (int(t) for t in region)
+    if not _is_dev(out):
+        return ref.mg_smooth(u, out, omega, x0, nx, y0, ny, f, c0, c1)
+    _native.check(_native.lib().gmt_mg_smooth(x0, nx, y0, ny, u.data_ptr(), u.stride(0), *_ptr_ld(f), float(c0),
+                                              float(c1), float(omega), out.data_ptr(), out.stride(0), _stream(out)),
+                  "gmt_mg_smooth")
+    return out
+
+
+def mg_smooth_path(u: torch.Tensor, out: torch.Tensor, region: tuple[int, int, int, int],
+                   f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`mg_smooth` would launch (gmt_mg_smooth_path, no launch):
+    ``(PATH_ROW_WALK or PATH_SCALAR, rows per segment of the row walk)``."""
+    x0, nx, _, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_mg_smooth_path(x0, nx, ny, u.data_ptr(), u.stride(0), *_ptr_ld(f), out.data_ptr(),
+                                            out.stride(0), ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def mg_restrict(d: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
+                coarse: tuple[int, int], cs: float = 0.25) -> torch.Tensor:
+    """Full weighting of the fine field ``d`` over ``region = (x0, nx, y0, ny)``
+    into the coarse field ``sc`` at ``coarse = (cx0, cy0)`` (gmt_mg_restrict).
+    ``parity = (px, py)``: the region-relative fine index of the first coarse
+    column / row.  Bitwise :func:`reference.mg_restrict`.  Returns ``sc``."""
+    _check2d(d, "mg_restrict.d")
+    _check2d(sc, "mg_restrict.sc")
+    x0, nx, y0, ny = (int(t) for t in region)
+    (px, py), (cx0, cy0) = (int(t) for t in parity), (int(t) for t in coarse)
+    if not _is_dev(sc):
+        return ref.mg_restrict(d, sc, cs, x0, nx, y0, ny, px, py, cx0, cy0)
+    _native.check(_native.lib().gmt_mg_restrict(x0, nx, y0, ny, px, py, d.data_ptr(), d.stride(0), float(cs),
+                                                sc.data_ptr(), cx0, cy0, sc.stride(0), _stream(sc)),
+                  "gmt_mg_restrict")
+    return sc
+
+
+def mg_restrict_path(d: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int],
+                     coarse: tuple[int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`mg_restrict` would launch (no launch)."""
+    return int(_native.lib().gmt_mg_restrict_path(int(region[0]), int(coarse[0]), d.data_ptr(), d.stride(0),
+                                                  sc.data_ptr(), sc.stride(0)))
+
+
+def mg_prolong_add(e: torch.Tensor, u: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
+                   coarse: tuple[int, int]) -> torch.Tensor:
+    """``u += P e`` over the fine ``region = (x0, nx, y0, ny)``, P the bilinear
+    interpolation from the coarse field ``e`` whose first cell of the region is
+    at ``coarse = (cx0, cy0)`` (gmt_mg_prolong_add); ``parity`` as for
+    :func:`mg_restrict`.  Bitwise :func:`reference.mg_prolong_add`.  ``e`` and
+    ``u`` must not share storage.  Returns ``u``."""
+    _check2d(e, "mg_prolong_add.e")
+    _check2d(u, "mg_prolong_add.u")
+    if _overlap(e, u):
+        raise ValueError("mg_prolong_add: e and u must not share storage")
+    x0, nx, y0, ny = (int(t) for t in region)
+    (px, py), (cx0, cy0) = (int(t) for t in parity), (int(t) for t in coarse)
+    if not _is_dev(u):
+        return ref.mg_prolong_add(e, u, x0, nx, y0, ny, px, py, cx0, cy0)
+    _native.check(_native.lib().gmt_mg_prolong_add(x0, nx, y0, ny, px, py, e.data_ptr(), cx0, cy0, e.stride(0),
+                                                   u.data_ptr(), u.stride(0), _stream(u)), "gmt_mg_prolong_add")
+    return u
+
+
+def mg_prolong_add_path(e: torch.Tensor, u: torch.Tensor, region: tuple[int, int, int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`mg_prolong_add` would launch (no launch)."""
+    return int(_native.lib().gmt_mg_prolong_add_path(int(region[0]), e.data_ptr(), e.stride(0), u.data_ptr(),
+                                                     u.stride(0)))
+
+
 def jacobi5_rects(u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],
                   f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> None:
     """Sweep up to 4 rectangles (the boundary frame of an overlapped step) in one launch."""

@@ -172,6 +172,88 @@ def cheby_step(u: torch.Tensor, v: torch.Tensor, w: float, x0: int, nx: int, y0:
     return v
 
 
+def mg_smooth(u, out, omega: float, x0: int, nx: int, y0: int, ny: int, f=None, c0: float = 0.25, c1: float = 1.0):
+    """gmt_mg_smooth: out = u + omega*(G(u) - u) over the region, every operation
+    rounded once.  Works on torch tensors and NumPy arrays alike."""
+    if nx < 0 or ny < 0:
+        raise ValueError("mg_smooth: negative extent")
+    if nx > 0 and ny > 0:
+        ys, xs = slice(y0, y0 + ny), slice(x0, x0 + nx)
+        o = c0 * ((u[ys, x0 - 1 : x0 - 1 + nx] + u[ys, x0 + 1 : x0 + 1 + nx])
+                  + (u[y0 - 1 : y0 - 1 + ny, xs] + u[y0 + 1 : y0 + 1 + ny, xs]))
+        if f is not None:
+            o = o + c1 * f[ys, xs]
+        c = u[ys, xs]
+        t = o - c
+        out[ys, xs] = c + omega * t
+    return out
+
+
+def mg_coarse_extent(n: int, p: int) -> int:
+    """Coarse cells of a fine region of n cells whose first coarse point has the region-relative index p."""
+    return (n - p + 1) // 2
+
+
+def mg_restrict(d, sc, cs: float, x0: int, nx: int, y0: int, ny: int, px: int, py: int, cx0: int, cy0: int):
+    """gmt_mg_restrict: full weighting of d over the fine region into the
+    ``mx x my`` coarse cells of sc at (cx0, cy0):
+    ``cs*((H(y-1) + H(y+1)) + 2*H(y))``, ``H(r) = (d[r][x-1] + d[r][x+1]) + 2*d[r][x]``."""
+    if nx < 0 or ny < 0 or px not in (0, 1) or py not in (0, 1):
+        raise ValueError("mg_restrict: negative extent or a parity outside 0..1")
+    mx, my = mg_coarse_extent(nx, px), mg_coarse_extent(ny, py)
+    if nx > 0 and ny > 0 and mx > 0 and my > 0:
+        xc, yc = x0 + px, y0 + py  # the first coarse point's fine cell
+
+        def h(r):
+            ys = slice(r, r + 2 * my - 1, 2)
+            return (d[ys, xc - 1 : xc - 1 + 2 * mx - 1 : 2] + d[ys, xc + 1 : xc + 1 + 2 * mx - 1 : 2]) \
+                + 2.0 * d[ys, xc : xc + 2 * mx - 1 : 2]
+
+        sc[cy0 : cy0 + my, cx0 : cx0 + mx] = cs * ((h(yc - 1) + h(yc + 1)) + 2.0 * h(yc))
+    return sc
+
+
+def mg_prolong_add(e, u, x0: int, nx: int, y0: int, ny: int, px: int, py: int, cx0: int, cy0: int):
+    """gmt_mg_prolong_add: u += bilinear interpolation of the coarse field e over
+    the fine region; by position: ``u + e``, ``u + 0.5*(eW + eE)``,
+    ``u + 0.5*(eS + eN)``, ``u + 0.25*((eSW + eSE) + (eNW + eNE))``."""
+    if nx < 0 or ny < 0 or px not in (0, 1) or py not in (0, 1):
+        raise ValueError("mg_prolong_add: negative extent or a parity outside 0..1")
+    if nx == 0 or ny == 0:
+        return u
+
+    def split(n, p, c0):
+        """fine indices on a coarse point with their coarse index; fine indices between two with the lower one's"""
+        on = list(range(p, n, 2))
+        bt = list(range(1 - p, n, 2))
+        return (on, [c0 + (i - p) // 2 for i in on]), (bt, [c0 + (i - p + 1) // 2 - 1 for i in bt])
+
+    (xon, Xon), (xbt, Xbt) = split(nx, px, cx0)
+    (yon, Yon), (ybt, Ybt) = split(ny, py, cy0)
+
+    def sel(rows, cols):
+        return (slice(rows[0], rows[-1] + 1, 2), slice(cols[0], cols[-1] + 1, 2)) if rows and cols else None
+
+    def at(Y, X, dy=0, dx=0):
+        return e[Y[0] + dy : Y[-1] + dy + 1, X[0] + dx : X[-1] + dx + 1]
+
+    fy = lambda idx: [y0 + j for j in idx]  # noqa: E731
+    fx = lambda idx: [x0 + i for i in idx]  # noqa: E731
+    s = sel(fy(yon), fx(xon))
+    if s:
+        u[s] = u[s] + at(Yon, Xon)
+    s = sel(fy(yon), fx(xbt))
+    if s:
+        u[s] = u[s] + 0.5 * (at(Yon, Xbt) + at(Yon, Xbt, 0, 1))
+    s = sel(fy(ybt), fx(xon))
+    if s:
+        u[s] = u[s] + 0.5 * (at(Ybt, Xon) + at(Ybt, Xon, 1, 0))
+    s = sel(fy(ybt), fx(xbt))
+    if s:
+        u[s] = u[s] + 0.25 * ((at(Ybt, Xbt) + at(Ybt, Xbt, 0, 1)) + (at(Ybt, Xbt, 1, 0) + at(Ybt, Xbt, 1, 1)))
+    return u
+
+
 def jacobi5xk(k: int, u: torch.Tensor, un: torch.Tensor, rects, dom, halo_mask: int = 0) -> None:
     """fp64 reference of k fused Laplace sweeps with the ghost-side rule of
     csrc/kernels/jacobi5tb.hip: a ring cell outside ``dom`` gets an
