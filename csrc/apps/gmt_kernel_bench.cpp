@@ -22,7 +22,8 @@
 //      alternated with gmt_daxpy on the same element count
 //      --only=mg [--reps=5] [--mg-n=N]: the kernels of a multigrid cycle
 //      (gmt_mg_smooth 16 B/fine point, 24 with f, gmt_mg_restrict 10,
-//      gmt_mg_prolong_add 18) on N x N (odd, default 8191), as --only=cg
+//      gmt_mg_prolong_add 18) on N x N (default 8191; an even N times them at
+//      N - 1 and the table-driven transfers of coarsen = any at N), as --only=cg
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -507,9 +508,11 @@ int main(int argc, char** argv) {
     // from the compulsory bytes per fine point: smooth 16 (24 with f), restrict
     // 8 + 2, prolong_add 16 + 2.
     const int reps = static_cast<int>(cli.geti("reps", 5));
-    const int64_t n = cli.geti("mg-n", 8191), m = (n - 1) / 2;
-    if (n < 3 || n % 2 == 0) {
-      std::printf("ERROR: --mg-n must be odd and >= 3\n");
+    // an even --mg-n = N: the nested kernels at N - 1 and, in the same process,
+    // the table-driven transfers of coarsen = any at N x N -> (N/2 - 1)^2
+    const int64_t nt = cli.geti("mg-n", 8191), n = nt % 2 == 0 ? nt - 1 : nt, m = (n - 1) / 2;
+    if (n < 3) {
+      std::printf("ERROR: --mg-n must be >= 3\n");
       return 1;
     }
     const int64_t xo = 8, ld = ((xo + n + 1 + 63) / 64) * 64, ldc = ((xo + m + 1 + 63) / 64) * 64;
@@ -540,24 +543,65 @@ int main(int argc, char** argv) {
     const std::function<void()> daxpy = [&] { GMT_CHECK("daxpy", gmt_daxpy(n * n, 1e-3, f.data(), u.data(), s)); };
     const char* name[4] = {"mg_smooth", "mg_smooth_f", "mg_restrict", "mg_prolong_add"};
     const double bytes[4] = {16.0, 24.0, 10.0, 18.0};
-    for (int k = 0; k < 4; ++k) {
-      if (k == 3) GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
+    // one kernel against DAXPY on npts elements, in the order A B B A
+    auto compare = [&](const char* nm, int idx, const std::function<void()>& fn, const std::function<void()>& dax,
+                       double bytes_pt, int64_t side) {
       Stats st[2];
       const int order[4] = {0, 1, 1, 0};
       for (int rep = 0; rep < reps; ++rep)
         for (int o = 0; o < 4; ++o) {
           const int w = order[o];
-          const double ms = time_ms(s, iters, w == 0 ? kernel[k] : daxpy);
+          const double ms = time_ms(s, iters, w == 0 ? fn : dax);
           st[w].add(ms);
-          std::printf("mg %lldx%lld rep %d  %-14s %9.4f ms\n", (long long)n, (long long)n, rep,
-                      w == 0 ? name[k] : "daxpy", ms);
+          std::printf("mg %lldx%lld rep %d  %-18s %9.4f ms\n", (long long)side, (long long)side, rep,
+                      w == 0 ? nm : "daxpy", ms);
         }
       char shape[64];
-      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
-      report(name[k], 0, shape, st[0].min(), bytes[k] * n * n);
-      report("daxpy", k + 1, shape, st[1].min(), 24.0 * n * n);
-      std::printf("mg %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)n, (long long)n, name[k],
-                  (bytes[k] / st[0].min()) / (24.0 / st[1].min()), reps);
+      std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)side, (long long)side);
+      report(nm, 0, shape, st[0].min(), bytes_pt * side * side);
+      report("daxpy", idx + 1, shape, st[1].min(), 24.0 * side * side);
+      std::printf("mg %lldx%lld  %s GB/s / daxpy GB/s = %.4f  (best of %d)\n", (long long)side, (long long)side, nm,
+                  (bytes_pt / st[0].min()) / (24.0 / st[1].min()), reps);
+      return st[0].min();
+    };
+    double best[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; ++k) {
+      if (k == 3) GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
+      best[k] = compare(name[k], k, kernel[k], daxpy, bytes[k], n);
+    }
+    if (nt % 2 == 0) {
+      // the general transfers on nt x nt: d with room for a 2-wide ring (interior origin (8, 2)), the same
+      // compulsory bytes per fine point as the nested pair; each beside DAXPY on nt * nt elements and beside
+      // the nested kernel's best time above
+      const int64_t mt = nt / 2 - 1;
+      const int64_t ldt = ((xo + nt + 2 + 63) / 64) * 64, ldct = ((xo + mt + 1 + 63) / 64) * 64;
+      const size_t telems = static_cast<size_t>(ldt) * (nt + 4);
+      Buffer<double> dt(telems, GMT_SPACE_DEVICE), vt(telems, GMT_SPACE_DEVICE), ft(telems, GMT_SPACE_DEVICE),
+          et(static_cast<size_t>(ldct) * (mt + 2), GMT_SPACE_DEVICE);
+      GMT_CHECK("fill", gmt_fill_poly(0, ldt, nt + 4, 0.0, 1e-5, 0.0, 1e-5, dt.data(), ldt, s));
+      GMT_CHECK("fill", gmt_fill_poly(0, ldt, nt + 4, 0.0, 1e-5, 0.0, 1e-5, vt.data(), ldt, s));
+      GMT_CHECK("fill", gmt_fill_poly(3, ldt, nt + 4, 0.0, 1e-9, 0.0, 0.0, ft.data(), ldt, s));
+      GMT_CHECK("fill", gmt_fill_poly(3, ldct, mt + 2, 0.0, 1e-12, 0.0, 0.0, et.data(), ldct, s));
+      GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+      const gmt_mg_xfer_desc desc{{nt, nt}, {mt, mt}, {0, 0}, {nt, nt}, {0, 0}, {mt, mt}};
+      void* plan = nullptr;
+      GMT_CHECK("plan", gmt_mg_xfer_plan_create(&desc, &plan));
+      std::printf("mg %lldx%lld  restrict_tab path %d, prolong_add_tab path %d, pitch %lld, coarse %lldx%lld pitch "
+                  "%lld\n", (long long)nt, (long long)nt, gmt_mg_restrict_tab_path(xo, xo, dt.data(), ldt, et.data(), ldct),
+                  gmt_mg_prolong_add_tab_path(xo, et.data(), ldct, vt.data(), ldt), (long long)ldt, (long long)mt,
+                  (long long)mt, (long long)ldct);
+      const std::function<void()> daxpyt = [&] { GMT_CHECK("daxpy", gmt_daxpy(nt * nt, 1e-3, ft.data(), dt.data(), s)); };
+      const double tr = compare("mg_restrict_tab", 4, [&] {
+        GMT_CHECK("mg_restrict_tab", gmt_mg_restrict_tab(plan, xo, 2, dt.data(), ldt, et.data(), xo, 1, ldct, s));
+      }, daxpyt, 10.0, nt);
+      GMT_CHECK("fill", gmt_fill_poly(3, ldct, mt + 2, 0.0, 1e-12, 0.0, 0.0, et.data(), ldct, s));
+      const double tp = compare("mg_prolong_add_tab", 5, [&] {
+        GMT_CHECK("mg_prolong_add_tab", gmt_mg_prolong_add_tab(plan, xo, 2, et.data(), xo, 1, ldct, vt.data(), ldt, s));
+      }, daxpyt, 18.0, nt);
+      GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+      gmt_mg_xfer_plan_destroy(plan);
+      std::printf("mg %lldx%lld  mg_restrict_tab ms / mg_restrict ms at %lld = %.4f, mg_prolong_add_tab ms / "
+                  "mg_prolong_add ms = %.4f\n", (long long)nt, (long long)nt, (long long)n, tr / best[2], tp / best[3]);
     }
   }
   if (only.find("pack") != std::string::npos) {

@@ -58,7 +58,7 @@
 //                           converges more slowly, an under-estimate can stagnate).  --check runs
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
-//   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C]
+//   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any]
 //                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
 //                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
 //                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
@@ -81,6 +81,7 @@
 #include "gmt/comm.hpp"
 #include "gmt/device.hpp"
 #include "gmt/jacobi.hpp"
+#include "gmt/mg_tab.hpp"
 #include "gmt/util.hpp"
 
 using namespace gmt;
@@ -262,8 +263,9 @@ static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const M
   std::vector<Level> lv(levels);
   for (int l = 0; l < levels; ++l) {
     Level& v = lv[l];
-    v.ny = l == 0 ? ny : (lv[l - 1].ny - 1) / 2;
-    v.nx = l == 0 ? nx : (lv[l - 1].nx - 1) / 2;
+    // coarsen = any: mg_coarse_extent per axis, (n - 1)/2 on an odd one as under the nested rule
+    v.ny = l == 0 ? ny : mg_coarse_extent(lv[l - 1].ny);
+    v.nx = l == 0 ? nx : mg_coarse_extent(lv[l - 1].nx);
     v.ld = v.nx + 2;
     v.has_s = l > 0 || source != 0;
     for (auto* f : {&v.u[0], &v.u[1], &v.s, &v.d}) f->assign((v.ny + 2) * v.ld, 0.0);
@@ -319,30 +321,81 @@ static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const M
     for (int64_t j = 1; j <= v.ny; ++j)
       for (int64_t i = 1; i <= v.nx; ++i) v.d[j * ld + i] = sweep(v.u[cur], j * ld + i) - v.u[cur][j * ld + i];
     Level& c = lv[l + 1];
-    auto h = [&](int64_t k) { return (v.d[k - 1] + v.d[k + 1]) + 2.0 * v.d[k]; };
-    for (int64_t J = 1; J <= c.ny; ++J)
-      for (int64_t I = 1; I <= c.nx; ++I) {
-        const int64_t k = 2 * J * ld + 2 * I;  // coarse point (J-1, I-1) sits on fine interior point (2J-1, 2I-1)
-        c.s[J * c.ld + I] = 0.25 * ((h(k - ld) + h(k + ld)) + 2.0 * h(k));
-      }
+    // a level with an even extent is not nested: the table-driven transfers of
+    // gmt_mg_restrict_tab / gmt_mg_prolong_add_tab over the whole level
+    const bool tab = v.ny % 2 == 0 || v.nx % 2 == 0;
+    MgAxisTab tx, ty;
+    if (tab && (mg_axis_tab_build(v.nx, c.nx, 0, v.nx, 0, c.nx, &tx) != 0 ||
+                mg_axis_tab_build(v.ny, c.ny, 0, v.ny, 0, c.ny, &ty) != 0)) {
+      std::printf("ERROR: serial multigrid: level %d has no transfer tables\n", l);
+      std::exit(1);
+    }
+    if (tab) {
+      auto hrow = [&](const double* q, const double* w, int cnt) {
+        volatile double a0 = w[0] * q[0], a1 = w[1] * q[1], a2 = w[2] * q[2];
+        double r = (a0 + a1) + a2;
+        if (cnt == 4) {
+          volatile double a3 = w[3] * q[3];
+          r = r + a3;
+        }
+        return r;
+      };
+      for (int64_t J = 0; J < c.ny; ++J)
+        for (int64_t I = 0; I < c.nx; ++I) {
+          const double *wx = &tx.rw[4 * I], *wy = &ty.rw[4 * J];
+          const int cx = tx.rf[2 * I + 1], cy = ty.rf[2 * J + 1];
+          const double* q = &v.d[(1 + ty.rf[2 * J]) * ld + 1 + tx.rf[2 * I]];
+          volatile double a0 = wy[0] * hrow(q, wx, cx), a1 = wy[1] * hrow(q + ld, wx, cx),
+                          a2 = wy[2] * hrow(q + 2 * ld, wx, cx);
+          double r = (a0 + a1) + a2;
+          if (cy == 4) {
+            volatile double a3 = wy[3] * hrow(q + 3 * ld, wx, cx);
+            r = r + a3;
+          }
+          c.s[(J + 1) * c.ld + I + 1] = r;
+        }
+    } else {
+      auto h = [&](int64_t k) { return (v.d[k - 1] + v.d[k + 1]) + 2.0 * v.d[k]; };
+      for (int64_t J = 1; J <= c.ny; ++J)
+        for (int64_t I = 1; I <= c.nx; ++I) {
+          const int64_t k = 2 * J * ld + 2 * I;  // coarse point (J-1, I-1) sits on fine interior point (2J-1, 2I-1)
+          c.s[J * c.ld + I] = 0.25 * ((h(k - ld) + h(k + ld)) + 2.0 * h(k));
+        }
+    }
     std::fill(c.u[0].begin(), c.u[0].end(), 0.0);
     const std::vector<double>& e = c.u[cycle(l + 1, 0)];
     std::vector<double>& u = v.u[cur];
-    for (int64_t j = 1; j <= v.ny; ++j)
-      for (int64_t i = 1; i <= v.nx; ++i) {
-        const bool ony = j % 2 == 0, onx = i % 2 == 0;
-        const double* p = &e[(ony ? j / 2 : (j - 1) / 2) * c.ld + (onx ? i / 2 : (i - 1) / 2)];
-        double t;
-        if (onx && ony)
-          t = p[0];
-        else if (ony)
-          t = 0.5 * (p[0] + p[1]);
-        else if (onx)
-          t = 0.5 * (p[0] + p[c.ld]);
-        else
-          t = 0.25 * ((p[0] + p[1]) + (p[c.ld] + p[c.ld + 1]));
-        u[j * ld + i] = u[j * ld + i] + t;
-      }
+    if (tab) {
+      for (int64_t j = 0; j < v.ny; ++j)
+        for (int64_t i = 0; i < v.nx; ++i) {
+          const double* q = &e[(1 + ty.pq[j]) * c.ld + 1 + tx.pq[i]];
+          const double t1x = tx.pt[i], t1y = ty.pt[j];
+          const double w0x = 1.0 - t1x, w0y = 1.0 - t1y;
+          volatile double b0 = w0x * q[0], b1 = t1x * q[1];
+          const double bot = b0 + b1;
+          volatile double t0 = w0x * q[c.ld], t1 = t1x * q[c.ld + 1];
+          const double top = t0 + t1;
+          volatile double vb = w0y * bot, vt = t1y * top;
+          const double add = vb + vt;
+          u[(j + 1) * ld + i + 1] = u[(j + 1) * ld + i + 1] + add;
+        }
+    } else {
+      for (int64_t j = 1; j <= v.ny; ++j)
+        for (int64_t i = 1; i <= v.nx; ++i) {
+          const bool ony = j % 2 == 0, onx = i % 2 == 0;
+          const double* p = &e[(ony ? j / 2 : (j - 1) / 2) * c.ld + (onx ? i / 2 : (i - 1) / 2)];
+          double t;
+          if (onx && ony)
+            t = p[0];
+          else if (ony)
+            t = 0.5 * (p[0] + p[1]);
+          else if (onx)
+            t = 0.5 * (p[0] + p[c.ld]);
+          else
+            t = 0.25 * ((p[0] + p[1]) + (p[c.ld] + p[c.ld + 1]));
+          u[j * ld + i] = u[j * ld + i] + t;
+        }
+    }
     for (int i = 0; i < o.nu2; ++i) relax(o.omega, false);
     return cur;
   };
@@ -462,6 +515,13 @@ int main(int argc, char** argv) {
     mo.omega = std::atof(cli.get("omega", "0.8").c_str());
     mo.max_levels = static_cast<int>(cli.geti("levels", 0));
     mo.coarse_iters = static_cast<int>(cli.geti("coarse-iters", 0));
+    const std::string coarsen = cli.get("coarsen", "nested");
+    if (coarsen != "nested" && coarsen != "any") {
+      if (rank == 0) std::printf("ERROR: --coarsen must be nested or any\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    mo.coarsen = coarsen == "any" ? 1 : 0;
     if (!nu_ok || mo.nu1 < 0 || mo.nu2 < 0 || mo.nu1 + mo.nu2 == 0 || !(mo.omega > 0 && mo.omega <= 1) ||
         mo.max_levels < 0 || mo.max_levels == 1 || mo.coarse_iters < 0) {
       if (rank == 0)
@@ -470,14 +530,16 @@ int main(int argc, char** argv) {
       std::fflush(stdout);
       MPI_Abort(MPI_COMM_WORLD, 1);
     }
-    if (!c.periodic && mg_level_table(c.ny_global, c.nx_global, c.py, c.px, mo.max_levels).size() < 2) {
+    if (!c.periodic && mg_level_table(c.ny_global, c.nx_global, c.py, c.px, mo.max_levels, mo.coarsen).size() < 2) {
       if (rank == 0) {
-        if (c.ny_global % 2 == 0 || c.nx_global % 2 == 0)
+        if (mo.coarsen == 0 && (c.ny_global % 2 == 0 || c.nx_global % 2 == 0))
           std::printf("ERROR: --mg has no coarse level for %lld x %lld: nx + 1 and ny + 1 must be even (8191 and "
-                      "32767 coarsen, 8192 does not)\n", (long long)c.ny_global, (long long)c.nx_global);
+                      "32767 coarsen, 8192 does not), or pass --coarsen=any\n", (long long)c.ny_global,
+                      (long long)c.nx_global);
         else
-          std::printf("ERROR: --mg has no coarse level for %lld x %lld on a %dx%d grid: a rank would own no coarse "
-                      "point\n", (long long)c.ny_global, (long long)c.nx_global, c.py, c.px);
+          std::printf("ERROR: --mg has no coarse level for %lld x %lld on a %dx%d grid: %sa rank would own no coarse "
+                      "point\n", (long long)c.ny_global, (long long)c.nx_global, c.py, c.px,
+                      mo.coarsen ? "the extents are too small or " : "");
       }
       std::fflush(stdout);
       MPI_Abort(MPI_COMM_WORLD, 1);
@@ -751,6 +813,7 @@ int main(int argc, char** argv) {
         std::printf("levels    = %d (coarsest %lld x %lld, %d iterations, rho %.6g)\n", mr.levels,
                     (long long)mr.coarse_ny, (long long)mr.coarse_nx, mr.coarse_iters, mr.coarse_rho);
         std::printf("cycle     = V(%d,%d), omega %g\n", mo.nu1, mo.nu2, mo.omega);
+        std::printf("coarsen   = %s\n", mo.coarsen ? "any" : "nested");
       }
       if (cg_fixed)
         std::printf("solve     = fixed count, %s norm, check every %d %ss\n", co.norm ? "max" : "l2",
@@ -818,7 +881,8 @@ int main(int argc, char** argv) {
       j.add("converged", sr.converged != 0).add("sweeps", sr.iters).add("residual_sweeps", sr.residual_iters)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
     if (mg_mode)
-      j.add("solver", "multigrid").add("levels", mr.levels).add("cycles", mr.iters)
+      j.add("solver", "multigrid").add("coarsen", mo.coarsen ? "any" : "nested").add("levels", mr.levels)
+          .add("cycles", mr.iters)
           .add("residual_cycles", mr.residual_iters).add("checks", mr.checks).add("converged", mr.converged != 0)
           .add("solve_ms", solve_ms).add("r0", mr.r0).add("residual_max", mr.residual_max);
     else if (cg_mode)

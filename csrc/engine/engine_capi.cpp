@@ -283,6 +283,7 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   mo.omega = o->omega;
   mo.max_levels = o->max_levels;
   mo.coarse_iters = o->coarse_iters;
+  mo.coarsen = o->coarsen;
   gmt::MgResult r;
   try {
     r = s.mg(mo);
@@ -299,6 +300,16 @@ int gmt_engine_mg_coarse_iters(double rho) { return gmt::mg_coarse_iters(rho); }
 int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels, int64_t* out, int max) {
   if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || !out) return -1;
   const auto t = gmt::mg_level_table(ny, nx, py, px, max_levels);
+  for (int i = 0; i < static_cast<int>(t.size()) && i < max; ++i) {
+    out[2 * i] = t[i].first;
+    out[2 * i + 1] = t[i].second;
+  }
+  return static_cast<int>(t.size());
+}
+int gmt_engine_mg_levels2(int64_t ny, int64_t nx, int py, int px, int max_levels, int coarsen, int64_t* out,
+                          int max) {
+  if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || coarsen < 0 || coarsen > 1 || !out) return -1;
+  const auto t = gmt::mg_level_table(ny, nx, py, px, max_levels, coarsen);
   for (int i = 0; i < static_cast<int>(t.size()) && i < max; ++i) {
     out[2 * i] = t[i].first;
     out[2 * i + 1] = t[i].second;

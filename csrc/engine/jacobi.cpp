@@ -2,6 +2,7 @@
 #include "gmt/jacobi.hpp"
 #include "gmt/control.hpp"
 #include "gmt/kernels.h"
+#include "gmt/mg_tab.hpp"
 #include "gmt/util.hpp"
 
 #include <algorithm>
@@ -1347,66 +1348,120 @@ int mg_coarse_iters(double rho) {
   }
 }
 
-std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels) {
-  std::vector<std::pair<int64_t, int64_t>> out{{ny, nx}};
-  // the share boundaries of either axis; a coarser level halves them
-  auto bounds = [](int64_t n, int p) {
-    std::vector<int64_t> b(static_cast<size_t>(p) + 1, n);
-    for (int i = 0; i < p; ++i) {
-      int64_t len = 0;
-      block_split(n, p, i, &b[i], &len);
-    }
-    return b;
-  };
+namespace {
+
+// One level of a hierarchy: the global extents and the share boundaries of
+// either axis (rank k of the axis owns cells b[k] .. b[k+1] - 1, 0-based).
+struct MgShape {
+  int64_t ny = 0, nx = 0;
+  std::vector<int64_t> by, bx;
+};
+
+std::vector<int64_t> mg_bounds(int64_t n, int p) {
+  std::vector<int64_t> b(static_cast<size_t>(p) + 1, n);
+  for (int i = 0; i < p; ++i) {
+    int64_t len = 0;
+    block_split(n, p, i, &b[i], &len);
+  }
+  return b;
+}
+
+// One axis of a coarsen = any level: the coarse share boundaries by the anchor
+// rule of gmt/mg_tab.hpp; false when a rank would own no coarse point, or,
+// on a level with table-driven transfers, when a rank's tables fail their
+// checks (tap count, tap halo, coarse ring) or a rank with a neighbour has
+// fewer than kMgTapHalo cells to send.
+bool mg_any_axis(int64_t n, int64_t m, const std::vector<int64_t>& b, bool tables, std::vector<int64_t>* cb) {
+  const size_t p = b.size() - 1;
+  cb->resize(p + 1);
+  for (size_t k = 0; k <= p; ++k) (*cb)[k] = mg_coarse_bound(n, m, b[k]);
+  for (size_t k = 0; k < p; ++k) {
+    if ((*cb)[k + 1] <= (*cb)[k]) return false;
+    if (!tables) continue;
+    if (p > 1 && b[k + 1] - b[k] < kMgTapHalo) return false;
+    MgAxisTab tab;
+    if (mg_axis_tab_build(n, m, b[k], b[k + 1] - b[k], (*cb)[k], (*cb)[k + 1] - (*cb)[k], &tab) != 0) return false;
+  }
+  return true;
+}
+
+std::vector<MgShape> mg_hierarchy(int64_t ny, int64_t nx, int py, int px, int max_levels, int coarsen) {
+  std::vector<MgShape> out(1);
+  out[0].ny = ny, out[0].nx = nx;
+  out[0].by = mg_bounds(ny, py), out[0].bx = mg_bounds(nx, px);
+  // nested: a coarser level halves the share boundaries
   auto halve = [](std::vector<int64_t>& b) {
     for (auto& v : b) v /= 2;
     for (size_t i = 0; i + 1 < b.size(); ++i)
       if (b[i + 1] <= b[i]) return false;  // a rank without a coarse row / column
     return true;
   };
-  std::vector<int64_t> by = bounds(ny, py), bx = bounds(nx, px);
-  while ((max_levels == 0 || static_cast<int>(out.size()) < max_levels) && ny % 2 == 1 && nx % 2 == 1) {
-    if (!halve(by) || !halve(bx)) break;
-    ny = (ny - 1) / 2;
-    nx = (nx - 1) / 2;
-    out.emplace_back(ny, nx);
+  while (max_levels == 0 || static_cast<int>(out.size()) < max_levels) {
+    const MgShape& f = out.back();
+    MgShape c;
+    if (coarsen == 0) {
+      if (f.ny % 2 == 0 || f.nx % 2 == 0) break;
+      c.by = f.by, c.bx = f.bx;
+      if (!halve(c.by) || !halve(c.bx)) break;
+      c.ny = (f.ny - 1) / 2, c.nx = (f.nx - 1) / 2;
+    } else {
+      c.ny = mg_coarse_extent(f.ny), c.nx = mg_coarse_extent(f.nx);
+      if (c.ny < 1 || c.nx < 1) break;
+      const bool tables = f.ny % 2 == 0 || f.nx % 2 == 0;
+      if (!mg_any_axis(f.ny, c.ny, f.by, tables, &c.by) || !mg_any_axis(f.nx, c.nx, f.bx, tables, &c.bx)) break;
+    }
+    out.push_back(std::move(c));
   }
   return out;
 }
 
-std::unique_ptr<Halo2D> JacobiSolver::ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny,
-                                                int64_t ld, bool corners) {
-  Neighbors nb = nb_;
-  if (!corners) nb.sw = nb.se = nb.nw = nb.ne = -2;
-  Span2D<double> f(field + (yo - 1) * ld + (xo - 1), nx + 2, ny + 2, ld);
-  return std::make_unique<Halo2D>(t_, f, 1, 1, nb, false, GMT_SPACE_DEVICE, corners);
+}  // namespace
+
+std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels,
+                                                        int coarsen) {
+  std::vector<std::pair<int64_t, int64_t>> out;
+  for (const MgShape& l : mg_hierarchy(ny, nx, py, px, max_levels, coarsen)) out.emplace_back(l.ny, l.nx);
+  return out;
 }
 
-// Every level the problem has (mg_level_table without a limit); a call with
-// max_levels uses the first of them.
+std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels) {
+  return mg_level_table(ny, nx, py, px, max_levels, 0);
+}
+
+std::unique_ptr<Halo2D> JacobiSolver::ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny,
+                                                int64_t ld, bool corners, int width) {
+  Neighbors nb = nb_;
+  if (!corners) nb.sw = nb.se = nb.nw = nb.ne = -2;
+  Span2D<double> f(field + (yo - width) * ld + (xo - width), nx + 2 * width, ny + 2 * width, ld);
+  return std::make_unique<Halo2D>(t_, f, width, width, nb, false, GMT_SPACE_DEVICE, corners);
+}
+
+// Every level the problem has under mgc_ (mg_hierarchy without a limit); a
+// call with max_levels uses the first of them.
 void JacobiSolver::mg_setup() {
-  if (!mg_.empty()) return;
+  std::vector<MgLevel>& mg = mg_[mgc_];
+  if (!mg.empty()) return;
   watchdog_kick("jacobi: mg set-up");
   cheby_setup();
-  const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, 0);
-  mg_.resize(table.size());
+  const auto shapes = mg_hierarchy(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, 0, mgc_);
+  const int cy = t_.rank() / cfg_.px, cx = t_.rank() % cfg_.px;
+  mg.resize(shapes.size());
   auto zeroed = [&](size_t elems) {
     Buffer<double> b(elems, GMT_SPACE_DEVICE);
     GMT_CHECK("memset", gmt_rt_memset_async(b.data(), 0, b.bytes(), s_));
     return b;
   };
-  for (size_t l = 0; l < mg_.size(); ++l) {
-    MgLevel& L = mg_[l];
-    L.ny_g = table[l].first;
-    L.nx_g = table[l].second;
+  for (size_t l = 0; l < mg.size(); ++l) {
+    MgLevel& L = mg[l];
+    L.ny_g = shapes[l].ny;
+    L.nx_g = shapes[l].nx;
     size_t elems = static_cast<size_t>(ld_) * (ny_ + 2 * g_);
     if (l == 0) {
       L.nx = nx_, L.ny = ny_, L.ox = ox_, L.oy = oy_;
       L.xo = xo_, L.yo = yo_, L.ld = ld_;
     } else {
-      const MgLevel& P = mg_[l - 1];
-      L.ox = P.ox / 2, L.nx = (P.ox + P.nx) / 2 - L.ox;
-      L.oy = P.oy / 2, L.ny = (P.oy + P.ny) / 2 - L.oy;
+      L.ox = shapes[l].bx[cx], L.nx = shapes[l].bx[cx + 1] - L.ox;
+      L.oy = shapes[l].by[cy], L.ny = shapes[l].by[cy + 1] - L.oy;
       L.xo = 8, L.yo = 1, L.ld = round_up(L.xo + L.nx + 1, 64);
       elems = static_cast<size_t>(L.ld) * (L.ny + 2);
       for (int b = 0; b < 2; ++b) {
@@ -1416,21 +1471,39 @@ void JacobiSolver::mg_setup() {
       L.s = zeroed(elems);
       L.sp = L.s.data();
     }
-    if (l + 1 < mg_.size()) L.d = zeroed(elems);
+    L.dyo = L.yo, L.dld = L.ld;
+    if (l + 1 == mg.size()) continue;
+    L.tab = L.ny_g % 2 == 0 || L.nx_g % 2 == 0;
+    if (L.tab) {  // room for the 2-wide ring of d, whatever the engine's ghost depth
+      L.dyo = std::max<int64_t>(L.yo, kMgTapHalo);
+      L.dld = std::max(L.ld, round_up(L.xo + L.nx + kMgTapHalo, 64));
+      elems = static_cast<size_t>(L.dld) * (L.dyo + L.ny + kMgTapHalo);
+    }
+    L.d = zeroed(elems);
   }
-  mg_ws_ = Buffer<double>(static_cast<size_t>(gmt_cg_workspace(nx_, ny_)) + 2, GMT_SPACE_DEVICE);
+  if (!mg_ws_.data())
+    mg_ws_ = Buffer<double>(static_cast<size_t>(gmt_cg_workspace(nx_, ny_)) + 2, GMT_SPACE_DEVICE);
   GMT_CHECK("mg set-up sync", gmt_rt_stream_synchronize(s_));
-  for (size_t l = 0; l < mg_.size(); ++l) {
-    MgLevel& L = mg_[l];
+  for (size_t l = 0; l < mg.size(); ++l) {
+    MgLevel& L = mg[l];
     if (l > 0)
       for (int b = 0; b < 2; ++b) L.hu[b] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true);
-    if (L.d.data()) L.hd = ring_halo(L.d.data(), L.xo, L.yo, L.nx, L.ny, L.ld, true);
+    if (!L.d.data()) continue;
+    L.hd = ring_halo(L.d.data(), L.xo, L.dyo, L.nx, L.ny, L.dld, true, L.tab ? kMgTapHalo : 1);
+    if (!L.tab) continue;
+    // the tables of this rank's share, checked on the host before they reach the device
+    const MgLevel& C = mg[l + 1];
+    const gmt_mg_xfer_desc desc{{L.nx_g, L.ny_g}, {C.nx_g, C.ny_g}, {L.ox, L.oy},
+                                {L.nx, L.ny},     {C.ox, C.oy},     {C.nx, C.ny}};
+    void* plan = nullptr;
+    GMT_CHECK("mg transfer plan", gmt_mg_xfer_plan_create(&desc, &plan));
+    L.plan.reset(plan);
   }
   watchdog_kick("jacobi: mg ready");
 }
 
 void JacobiSolver::mg_ring(int l) {
-  MgLevel& L = mg_[l];
+  MgLevel& L = mg_[mgc_][l];
   if (L.ring) return;
   Halo2D& h = l == 0 ? *cheby_halo_[L.cur] : *L.hu[L.cur];
   if (h.active()) {
@@ -1441,7 +1514,7 @@ void JacobiSolver::mg_ring(int l) {
 }
 
 void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho) {
-  MgLevel& L = mg_[l];
+  MgLevel& L = mg_[mgc_][l];
   const int64_t ldf = L.sp ? L.ld : 0;
   const double c1 = L.sp ? 1.0 : 0.0;
   if (l == levels - 1) {
@@ -1472,18 +1545,24 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
       L.ring = false;
     }
   };
-  MgLevel& C = mg_[l + 1];
+  MgLevel& C = mg_[mgc_][l + 1];
   const int px = L.ox % 2 == 0 ? 1 : 0, py = L.oy % 2 == 0 ? 1 : 0;
   smooth(o.nu1);
   mg_ring(l);
-  GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, L.d.data(),
-                                        L.ld, mg_ws_.data(), mg_ws_.data() + 2, s_));
+  // d in its own layout: row yo of u is row dyo of d
+  double* dv = L.d.data() + (L.dyo - L.yo) * L.dld;
+  GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, dv, L.dld,
+                                        mg_ws_.data(), mg_ws_.data() + 2, s_));
   if (L.hd->active()) {
     L.hd->start(s_);
     L.hd->finish(s_);
   }
-  GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
-                                           C.yo, C.ld, s_));
+  if (L.tab)
+    GMT_CHECK("mg restrict", gmt_mg_restrict_tab(L.plan.get(), L.xo, L.dyo, L.d.data(), L.dld, C.s.data(), C.xo, C.yo,
+                                                 C.ld, s_));
+  else
+    GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
+                                             C.yo, C.ld, s_));
   // u = 0 on the coarser level, ring included: current on every rank
   GMT_CHECK("memset", gmt_rt_memset_async(C.up[0], 0, C.u[0].bytes(), s_));
   C.cur = 0;
@@ -1495,8 +1574,12 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
     hc.finish(s_);
   }
   C.ring = true;
-  GMT_CHECK("mg prolong", gmt_mg_prolong_add(L.xo, L.nx, L.yo, L.ny, px, py, C.up[C.cur], C.xo, C.yo, C.ld,
-                                             L.up[L.cur], L.ld, s_));
+  if (L.tab)
+    GMT_CHECK("mg prolong", gmt_mg_prolong_add_tab(L.plan.get(), L.xo, L.yo, C.up[C.cur], C.xo, C.yo, C.ld,
+                                                   L.up[L.cur], L.ld, s_));
+  else
+    GMT_CHECK("mg prolong", gmt_mg_prolong_add(L.xo, L.nx, L.yo, L.ny, px, py, C.up[C.cur], C.xo, C.yo, C.ld,
+                                               L.up[L.cur], L.ld, s_));
   L.ring = false;
   smooth(o.nu2);
 }
@@ -1505,16 +1588,20 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   const CheckLoop loop{"mg", "max_cycles", "jacobi mg check", o.tol, o.rtol, o.norm, o.max_cycles,
                        o.check_every == 0 ? 1 : o.check_every, o.lag, false};
   loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
-                    o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0,
-                ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0");
+                    o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1),
+                ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0, "
+                "coarsen 0 or 1");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
-  const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels);
+  const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels, o.coarsen);
   if (table.size() < 2)
     throw std::invalid_argument(
         std::string("JacobiSolver::mg: no coarse level: ") +
-        (cfg_.ny_global % 2 == 0 || cfg_.nx_global % 2 == 0 ? "nx + 1 and ny + 1 must be even"
-                                                            : "a rank of the process grid would own no coarse point"));
+        (o.coarsen == 0 && (cfg_.ny_global % 2 == 0 || cfg_.nx_global % 2 == 0)
+             ? "nx + 1 and ny + 1 must be even"
+             : o.coarsen == 0 ? "a rank of the process grid would own no coarse point"
+                              : "the extents are too small or a rank of the process grid would own no coarse point"));
+  mgc_ = o.coarsen;
   mg_setup();
   const int levels = static_cast<int>(table.size());
   MgResult res;
@@ -1523,7 +1610,7 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   res.coarse_nx = table.back().second;
   res.coarse_rho = cheby_rho(res.coarse_nx, res.coarse_ny);
   res.coarse_iters = o.coarse_iters > 0 ? o.coarse_iters : mg_coarse_iters(res.coarse_rho);
-  MgLevel& F = mg_[0];
+  MgLevel& F = mg_[mgc_][0];
   for (int b = 0; b < 2; ++b) F.up[b] = buf_[b].data();
   F.sp = src_f();
   F.cur = parity_;

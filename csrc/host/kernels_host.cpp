@@ -16,9 +16,11 @@
 #include <thread>
 
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "gmt/kernels.h"
+#include "gmt/mg_tab.hpp"
 #include "gmt/tb_geom.h"
 
 extern "C" {
@@ -510,6 +512,96 @@ int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, i
       else
         t = 0.25 * ((p[0] + p[1]) + (p[lde] + p[lde + 1]));
       *q = *q + t;
+    }
+  return 0;
+}
+
+// the table-driven transfers: the plan is the host's tables themselves
+namespace {
+struct HostXferPlan {
+  gmt::MgAxisTab tab[2];
+  int64_t fn[2], cn[2];
+};
+}  // namespace
+
+int gmt_mg_xfer_plan_create(const gmt_mg_xfer_desc* desc, void** plan) {
+  if (plan) *plan = nullptr;
+  if (!desc || !plan) return 1;
+  auto p = std::make_unique<HostXferPlan>();
+  for (int a = 0; a < 2; ++a) {
+    if (gmt::mg_axis_tab_build(desc->n[a], desc->m[a], desc->fo[a], desc->fn[a], desc->co[a], desc->cn[a],
+                               &p->tab[a]) != 0)
+      return 1;
+    p->fn[a] = desc->fn[a];
+    p->cn[a] = desc->cn[a];
+  }
+  *plan = p.release();
+  return 0;
+}
+void gmt_mg_xfer_plan_destroy(void* plan) { delete static_cast<HostXferPlan*>(plan); }
+int gmt_mg_restrict_tab_path(int64_t, int64_t, const double*, int64_t, const double*, int64_t) {
+  return GMT_PATH_NONE;
+}
+int gmt_mg_prolong_add_tab_path(int64_t, const double*, int64_t, const double*, int64_t) { return GMT_PATH_NONE; }
+
+int gmt_mg_restrict_tab(const void* plan, int64_t x0, int64_t y0, const double* d, int64_t ldd, double* sc,
+                        int64_t cx0, int64_t cy0, int64_t ldc, void*) {
+  const auto* p = static_cast<const HostXferPlan*>(plan);
+  if (!p) return 1;
+  const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0], my = p->cn[1];
+  if (nx == 0 || ny == 0 || mx == 0 || my == 0) return 0;
+  if (!d || !sc || x0 < gmt::kMgTapHalo || y0 < gmt::kMgTapHalo || cx0 < 0 || cy0 < 0 ||
+      ldd < x0 + nx + gmt::kMgTapHalo || ldc < cx0 + mx)
+    return 1;
+  const gmt::MgAxisTab &tx = p->tab[0], &ty = p->tab[1];
+  auto h = [](const double* q, const double* w, int cnt) {
+    const double a0 = w[0] * q[0], a1 = w[1] * q[1], a2 = w[2] * q[2];
+    double v = (a0 + a1) + a2;
+    if (cnt == 4) {
+      const double a3 = w[3] * q[3];
+      v = v + a3;
+    }
+    return v;
+  };
+  for (int64_t J = 0; J < my; ++J)
+    for (int64_t I = 0; I < mx; ++I) {
+      const double *wx = &tx.rw[4 * I], *wy = &ty.rw[4 * J];
+      const int cx = tx.rf[2 * I + 1], cy = ty.rf[2 * J + 1];
+      const double* q = d + (y0 + ty.rf[2 * J]) * ldd + x0 + tx.rf[2 * I];
+      const double a0 = wy[0] * h(q, wx, cx), a1 = wy[1] * h(q + ldd, wx, cx), a2 = wy[2] * h(q + 2 * ldd, wx, cx);
+      double s = (a0 + a1) + a2;
+      if (cy == 4) {
+        const double a3 = wy[3] * h(q + 3 * ldd, wx, cx);
+        s = s + a3;
+      }
+      sc[(cy0 + J) * ldc + cx0 + I] = s;
+    }
+  return 0;
+}
+
+int gmt_mg_prolong_add_tab(const void* plan, int64_t x0, int64_t y0, const double* e, int64_t cx0, int64_t cy0,
+                           int64_t lde, double* u, int64_t ld, void*) {
+  const auto* p = static_cast<const HostXferPlan*>(plan);
+  if (!p) return 1;
+  const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0];
+  if (nx == 0 || ny == 0) return 0;
+  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < gmt::kMgRingHalo || cy0 < gmt::kMgRingHalo ||
+      lde < cx0 + mx + gmt::kMgRingHalo || ld < x0 + nx)
+    return 1;
+  const gmt::MgAxisTab &tx = p->tab[0], &ty = p->tab[1];
+  for (int64_t j = 0; j < ny; ++j)
+    for (int64_t i = 0; i < nx; ++i) {
+      const double* q = e + (cy0 + ty.pq[j]) * lde + cx0 + tx.pq[i];
+      const double t1x = tx.pt[i], t1y = ty.pt[j];
+      const double w0x = 1.0 - t1x, w0y = 1.0 - t1y;
+      const double b0 = w0x * q[0], b1 = t1x * q[1];
+      const double bot = b0 + b1;
+      const double t0 = w0x * q[lde], t1 = t1x * q[lde + 1];
+      const double top = t0 + t1;
+      const double vb = w0y * bot, vt = t1y * top;
+      const double v = vb + vt;
+      double* o = u + (y0 + j) * ld + x0 + i;
+      *o = *o + v;
     }
   return 0;
 }

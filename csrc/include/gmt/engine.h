@@ -135,6 +135,7 @@ typedef struct gmt_engine_mg_opts {
   double omega;     /* in (0, 1] */
   int max_levels;   /* 0 = no limit, else >= 2 */
   int coarse_iters; /* 0 = gmt_engine_mg_coarse_iters(rho of the coarsest level) */
+  int coarsen;      /* 0 nested (nx + 1 and ny + 1 even on every level), 1 any lattice size (MgOpts::coarsen) */
 } gmt_engine_mg_opts;
 typedef struct gmt_engine_mg_result {
   int converged, iters, checks, residual_iters;
@@ -155,6 +156,9 @@ int gmt_engine_mg_coarse_iters(double rho);
 /* global {ny, nx} of every level of an ny x nx problem on a py x px grid into
  * out[2 * max] (level 0 first); returns the number of levels */
 int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels, int64_t* out, int max);
+/* the same under gmt_engine_mg_opts.coarsen (0: the table above); -1 on a bad argument */
+int gmt_engine_mg_levels2(int64_t ny, int64_t nx, int py, int px, int max_levels, int coarsen, int64_t* out,
+                          int max);
 /* 1 when the engine has a periodic axis */
 int gmt_engine_jacobi_periodic(void* h);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,

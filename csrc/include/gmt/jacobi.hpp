@@ -42,6 +42,7 @@
 
 #include "gmt/buffer.hpp"
 #include "gmt/halo.hpp"
+#include "gmt/kernels.h"
 #include "gmt/transport.hpp"
 
 namespace gmt {
@@ -205,6 +206,22 @@ double cheby_next_weight(double rho2, double w, int k);
 //             u_coarse; nu2 sweeps.
 // The fine ring is the real Dirichlet ring, coarse rings are zero.  An
 // iteration is one cycle; criterion and lagged check are solve()'s.
+//
+// coarsen = 1 ("any") drops the nesting: each axis of each level is coarsened
+// on its own to m = mg_coarse_extent(n) points on the same interval, (n-1)/2
+// for odd n and n/2 - 1 for even n (8192 -> 4095 -> 2047 -> ... -> 1), with the
+// same rediscretised operator on every level.  A level whose two axes are odd
+// is the nested level above, kernels and all; any other level transfers by
+// linear interpolation P with position-dependent weights and its exact
+// transpose (gmt_mg_prolong_add_tab / gmt_mg_restrict_tab, tables of
+// gmt/mg_tab.hpp, an odd axis being the table with weights 0.5 / 1 / 0.5):
+// coarse point J belongs to the rank that owns fine cell floor(J*(n+1)/(m+1)),
+// and the residual of such a level is exchanged 2 wide with corners.  Set-up
+// computes every rank's needs from the tables: a level on which a coarse point
+// would have other than 3 or 4 taps per axis, a tap more than 2 cells or an
+// interpolated coarse cell more than 1 outside a rank's share, or a rank with
+// a neighbour and fewer than 2 cells on that axis, is not created, and the
+// hierarchy stops there.  The two hierarchies are built apart and never mixed.
 struct MgOpts {
   double tol = 0.0, rtol = 0.0;  // both 0: fixed-count mode, exactly max_cycles cycles
   int norm = 0;                  // 0: L2, 1: max |d|
@@ -215,6 +232,7 @@ struct MgOpts {
   double omega = 0.8;            // the damping, in (0, 1]
   int max_levels = 0;            // 0: as many as the extents and the process grid allow; else >= 2
   int coarse_iters = 0;          // Chebyshev iterations on the coarsest level (0 = mg_coarse_iters(rho))
+  int coarsen = 0;               // 0 nested; 1 any: every lattice size (both above)
 };
 struct MgResult : CheckResult {
   int levels = 0;                          // levels used, the fine one included
@@ -232,6 +250,9 @@ int mg_coarse_iters(double rho);
 // reached.  A function of the global extents and block_split only: every rank
 // computes the same table.
 std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels);
+// The same for MgOpts::coarsen (0: the table above, bit for bit).
+std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, int py, int px, int max_levels,
+                                                        int coarsen);
 
 class JacobiSolver {
  public:
@@ -412,10 +433,10 @@ class JacobiSolver {
                   const std::function<const double*(int)>& check);
   void cg_setup();          // the state of cg() (first use; collective)
   void cheby_setup();       // the halo plans of cheby() (first use; collective)
-  // the 1-wide ring of a field with corners, or its faces only (collective)
+  // the ring of a field, `width` cells wide, with corners, or its faces only (collective)
   std::unique_ptr<Halo2D> ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny, int64_t ld,
-                                    bool corners);
-  void mg_setup();          // the levels of mg() (first use; collective)
+                                    bool corners, int width = 1);
+  void mg_setup();          // the levels of mg() for mgc_ (first use; collective)
   void mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho);
   void mg_ring(int l);      // the faces of level l's current buffer hold the neighbours' current values
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
@@ -473,13 +494,19 @@ class JacobiSolver {
     int64_t nx = 0, ny = 0, ox = 0, oy = 0;            // this rank's share and its global offset
     int64_t xo = 8, yo = 1, ld = 0;                    // interior origin, pitch
     Buffer<double> u[2], s, d;                         // d: the residual (none on the last level)
+    // the transfer to the next level is table-driven: d then has its own
+    // layout (interior origin (xo, dyo), pitch dld, room for a 2-wide ring)
+    bool tab = false;
+    int64_t dyo = 1, dld = 0;
+    std::unique_ptr<void, void (*)(void*)> plan{nullptr, gmt_mg_xfer_plan_destroy};
     double* up[2] = {nullptr, nullptr};                // the level's buffer pair
     const double* sp = nullptr;                        // its source (level 0: NULL without one)
     int cur = 0;                                       // up[cur] is the level's current field
     bool ring = false;                                 // its faces are current
     std::unique_ptr<Halo2D> hu[2], hd;                 // rings with corners of u[0], u[1] and d
   };
-  std::vector<MgLevel> mg_;
+  std::vector<MgLevel> mg_[2];  // by MgOpts::coarsen
+  int mgc_ = 0;                 // the hierarchy the running mg() uses
   Buffer<double> mg_ws_;  // gmt_cg_apply's workspace and its two results (level 0's size)
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values

@@ -339,6 +339,55 @@ int gmt_mg_smooth_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int6
 int gmt_mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc);
 int gmt_mg_prolong_add_path(int64_t x0, const double* e, int64_t lde, const double* u, int64_t ld);
 
+/* ---- Table-driven transfers between two levels that are not nested: n fine
+ *      and m coarse interior points per axis on the same interval (any m with
+ *      3 or 4 fine points between the neighbours of a coarse one), linear
+ *      interpolation P with position-dependent weights and its exact transpose
+ *      R = P^T.  gmt/mg_tab.hpp defines the tables: fine point i (1-based,
+ *      global) lies between coarse points q and q + 1 with
+ *      q, r = divmod(i*(m+1), n+1), t = r/(n+1), weights 1.0 - t and t.
+ *
+ *      The tables reach a kernel only through a plan.  plan_create builds them
+ *      on the host from the description below, checks that every tap of the
+ *      coarse region lies within 2 fine cells of the fine region, that every
+ *      coarse cell the fine region interpolates from lies within 1 of the
+ *      coarse region and that every coarse point has 3 or 4 taps per axis, and
+ *      only then uploads them (a synchronous copy: not inside a capture).  A
+ *      description that fails is refused (non-zero, *plan = NULL): nothing it
+ *      describes is ever launched.  Index 0 of each pair is x, 1 is y. */
+typedef struct gmt_mg_xfer_desc {
+  int64_t n[2], m[2];   /* global fine and coarse interior points */
+  int64_t fo[2], fn[2]; /* the fine region: global cells fo+1 .. fo+fn (1-based) */
+  int64_t co[2], cn[2]; /* the coarse region: global cells co+1 .. co+cn */
+} gmt_mg_xfer_desc;
+int gmt_mg_xfer_plan_create(const gmt_mg_xfer_desc* desc, void** plan);
+void gmt_mg_xfer_plan_destroy(void* plan); /* NULL is allowed; not while a launch that uses it is in flight */
+/* restrict_tab: sc = P^T d.  d holds the plan's fine region at (x0, y0), sc its
+ *   coarse region at (cx0, cy0).  Per coarse cell, with the taps and weights
+ *   of its column (wx) and row (wy), per tapped fine row k
+ *   h_k = ((wx0*d0 + wx1*d1) + wx2*d2) [+ wx3*d3], then
+ *   s = ((wy0*h0 + wy1*h1) + wy2*h2) [+ wy3*h3]: the weights sum to about
+ *   (n+1)/(m+1) per axis, there is no separate scale.  Only real taps are
+ *   read: d on the region and up to 2 cells around it, corners included.
+ *   x0 and y0 >= 2, ldd >= x0 + nx + 2, cx0 and cy0 >= 0, ldc >= cx0 + mx.
+ * prolong_add_tab: u += P e on the plan's fine region at (x0, y0); e holds the
+ *   coarse region at (cx0, cy0).  Per fine cell, with (I, tx) of its column
+ *   and (J, ty) of its row, w0 = 1.0 - t:
+ *   bot = w0x*e[J][I] + tx*e[J][I+1]; top = w0x*e[J+1][I] + tx*e[J+1][I+1];
+ *   v = w0y*bot + ty*top; u = u + v.  All four coarse cells are always read:
+ *   e on the coarse region and its 1-wide ring, corners included.  x0 and
+ *   y0 >= 1, cx0 and cy0 >= 1, lde >= cx0 + mx + 1, ld >= x0 + nx.
+ * Both: asynchronous on `stream`, no contraction, bitwise the same on both
+ * backends; 0 with nothing launched for an empty region; refused (non-zero)
+ * with a NULL plan or field, a small origin or a short pitch.  The path
+ * queries follow gmt_mg_restrict_path / gmt_mg_prolong_add_path. */
+int gmt_mg_restrict_tab(const void* plan, int64_t x0, int64_t y0, const double* d, int64_t ldd, double* sc,
+                        int64_t cx0, int64_t cy0, int64_t ldc, void* stream);
+int gmt_mg_prolong_add_tab(const void* plan, int64_t x0, int64_t y0, const double* e, int64_t cx0, int64_t cy0,
+                           int64_t lde, double* u, int64_t ld, void* stream);
+int gmt_mg_restrict_tab_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc);
+int gmt_mg_prolong_add_tab_path(int64_t x0, const double* e, int64_t lde, const double* u, int64_t ld);
+
 /* ---- Temporal-blocking Jacobi (csrc/kernels/jacobi5tb.hip): `sweeps` fused
  *      Laplace sweeps per memory pass, un = J^sweeps(u), on up to 8 output
  *      rects {x0, nx, y0, ny} (absolute array coordinates, x0 >= sweeps,

@@ -15,12 +15,26 @@
 //   mg_prolong_pt       bilinear interpolation added in place: one lane per
 //                       fine pair, a 16-B read-modify-write of u, the coarse
 //                       cells by 8-B loads (L2 hits: four fine cells share them).
+//   mg_restrict_tab_pt  the transpose of linear interpolation between levels
+//   mg_prolong_tab_pt   that are not nested (any point count on the same
+//                       interval): the same 16-B stores and read-modify-write,
+//                       with the coarse cell and weight of a fine column / row,
+//                       and the 3 or 4 taps and weights of a coarse one, from
+//                       device tables that the host built and checked
+//                       (gmt/mg_tab.hpp); taps by 8-B loads out of L2.  The
+//                       restriction computes one coarse cell per lane and pairs
+//                       the lanes for the store.
 //   *_scalar            one cell per lane, for odd alignment or pitches.
 //
 // Every cell is evaluated without contraction, as the CPU backend's.
+#include <cstring>
+#include <new>
+#include <vector>
+
 #include "common.hpp"
 #include "row_walk.hpp"
 #include "gmt/kernels.h"
+#include "gmt/mg_tab.hpp"
 
 namespace gmt {
 
@@ -238,6 +252,158 @@ static int mg_prolong_path(int64_t x0, const double* e, int64_t lde, const doubl
   return x0 % 2 == 0 && walk_vec_ok(e, lde) && walk_vec_ok(u, ld) ? GMT_PATH_PT : GMT_PATH_SCALAR;
 }
 
+// ---- table-driven transfers between levels that are not nested (gmt/mg_tab.hpp) ----
+//
+// The tables of a plan: per fine column / row the coarse cell below it and t,
+// per coarse column / row {first tap, tap count} and four weights.  Every
+// index was checked on the host before the upload (gmt_mg_xfer_plan_create):
+// the kernels add them to the region's origin without a second look.  Table
+// bases are 16-B aligned and a lane's pair starts at an even entry, so the
+// pair's entries of the prolongation come by one 8-B and one 16-B load, a
+// coarse cell's by one 8-B and two 16-B loads, on any path; rows are uniform
+// over most of a wave.
+struct MgXferPlan {
+  int64_t fn[2] = {0, 0}, cn[2] = {0, 0};  // fine and coarse extents of the region, x then y
+  const int32_t* pq[2] = {nullptr, nullptr};
+  const double* pt[2] = {nullptr, nullptr};
+  const int2* rf[2] = {nullptr, nullptr};
+  const double* rw[2] = {nullptr, nullptr};
+  void* dev = nullptr;  // the one allocation behind them
+};
+
+// u' of one fine cell: p points at coarse cell (J, I) below / west of it
+__device__ __forceinline__ double mg_tab_prolong_cell(const double* __restrict__ p, int64_t lde, double tx, double ty,
+                                                      double u) {
+#pragma clang fp contract(off)
+  const double w0x = 1.0 - tx, w0y = 1.0 - ty;
+  const double b0 = w0x * p[0], b1 = tx * p[1];
+  const double bot = b0 + b1;
+  const double t0 = w0x * p[lde], t1 = tx * p[lde + 1];
+  const double top = t0 + t1;
+  const double vb = w0y * bot, vt = ty * top;
+  const double v = vb + vt;
+  return u + v;
+}
+
+// e0 at coarse cell (0, 0) of the region, u0 at fine cell (0, 0)
+__global__ __launch_bounds__(kBlock) void mg_prolong_tab_scalar(int64_t nx, int64_t ny,
+                                                                const int32_t* __restrict__ qx,
+                                                                const double* __restrict__ tx,
+                                                                const int32_t* __restrict__ qy,
+                                                                const double* __restrict__ ty,
+                                                                const double* __restrict__ e0, int64_t lde,
+                                                                double* __restrict__ u0, int64_t ld) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (t >= nx * ny) return;
+  const int64_t i = t % nx, j = t / nx;
+  double* q = u0 + j * ld + i;
+  *q = mg_tab_prolong_cell(e0 + static_cast<int64_t>(qy[j]) * lde + qx[i], lde, tx[i], ty[j], *q);
+}
+
+__global__ __launch_bounds__(kBlock) void mg_prolong_tab_pt(int64_t nx, int64_t ny, const int32_t* __restrict__ qx,
+                                                            const double* __restrict__ tx,
+                                                            const int32_t* __restrict__ qy,
+                                                            const double* __restrict__ ty,
+                                                            const double* __restrict__ e0, int64_t lde,
+                                                            double* __restrict__ u0, int64_t ld) {
+  const int64_t npx = (nx + 1) / 2;  // fine pairs per row
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (t >= npx * ny) return;
+  const int64_t i = 2 * (t % npx), j = t / npx;
+  const double* er = e0 + static_cast<int64_t>(qy[j]) * lde;
+  const double tyj = ty[j];
+  double* q = u0 + j * ld + i;
+  if (i + 1 < nx) {
+    const int2 I = *reinterpret_cast<const int2*>(qx + i);
+    const d2 tt = ld2(tx + i);
+    d2 v = ld2(q);
+    v.x = mg_tab_prolong_cell(er + I.x, lde, tt.x, tyj, v.x);
+    v.y = mg_tab_prolong_cell(er + I.y, lde, tt.y, tyj, v.y);
+    st2(q, v);
+  } else {
+    *q = mg_tab_prolong_cell(er + qx[i], lde, tx[i], tyj, *q);
+  }
+}
+
+// the weighted taps of one coarse column in one fine row: p at the first tap.
+// No branch: a column of three taps re-reads its third tap (a real one, so
+// nothing outside the read set is touched) and the sum without it is selected,
+// so every load of a lane can be in flight at once.
+__device__ __forceinline__ double mg_tab_h(const double* __restrict__ p, d2 wa, d2 wb, int cnt) {
+#pragma clang fp contract(off)
+  const bool four = cnt == 4;
+  const double d3 = p[four ? 3 : 2];
+  const double a0 = wa.x * p[0], a1 = wa.y * p[1], a2 = wb.x * p[2], a3 = wb.y * d3;
+  const double h = (a0 + a1) + a2;
+  const double h4 = h + a3;
+  return four ? h4 : h;
+}
+
+// one coarse cell: p at its first tap row and column; rows as columns
+__device__ __forceinline__ double mg_tab_restrict_cell(const double* __restrict__ p, int64_t ldd, d2 wxa, d2 wxb,
+                                                       int cx, d2 wya, d2 wyb, int cy) {
+#pragma clang fp contract(off)
+  const bool four = cy == 4;
+  const double h0 = mg_tab_h(p, wxa, wxb, cx), h1 = mg_tab_h(p + ldd, wxa, wxb, cx),
+               h2 = mg_tab_h(p + 2 * ldd, wxa, wxb, cx), h3 = mg_tab_h(p + (four ? 3 : 2) * ldd, wxa, wxb, cx);
+  const double a0 = wya.x * h0, a1 = wya.y * h1, a2 = wyb.x * h2, a3 = wyb.y * h3;
+  const double s = (a0 + a1) + a2;
+  const double s4 = s + a3;
+  return four ? s4 : s;
+}
+
+// d0 at fine cell (0, 0) of the region, s0 at coarse cell (0, 0)
+__global__ __launch_bounds__(kBlock) void mg_restrict_tab_scalar(int64_t mx, int64_t my, const int2* __restrict__ fx,
+                                                                 const double* __restrict__ wx,
+                                                                 const int2* __restrict__ fy,
+                                                                 const double* __restrict__ wy,
+                                                                 const double* __restrict__ d0, int64_t ldd,
+                                                                 double* __restrict__ s0, int64_t ldc) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= mx * my) return;
+  const int64_t I = i % mx, J = i / mx;
+  const int2 ax = fx[I], ay = fy[J];
+  const double* p = d0 + static_cast<int64_t>(ay.x) * ldd + ax.x;
+  s0[J * ldc + I] = mg_tab_restrict_cell(p, ldd, ld2(wx + 4 * I), ld2(wx + 4 * I + 2), ax.y, ld2(wy + 4 * J),
+                                         ld2(wy + 4 * J + 2), ay.y);
+}
+
+// One lane per coarse cell, not per pair: neighbouring lanes then tap fine cells
+// 16 B apart instead of 32, and a wave's 8-B loads touch half the cache lines
+// per coarse cell (measured at 8192^2: 0.30 ms with a pair per lane, 0.20 ms so).
+// The lanes of a coarse row are padded to an even count, so the two cells of a
+// pair sit in one wave: the odd lane hands its value over and the even lane
+// makes the pair's 16-B store.
+__global__ __launch_bounds__(kBlock) void mg_restrict_tab_pt(int64_t mx, int64_t my, const int2* __restrict__ fx,
+                                                             const double* __restrict__ wx,
+                                                             const int2* __restrict__ fy,
+                                                             const double* __restrict__ wy,
+                                                             const double* __restrict__ d0, int64_t ldd,
+                                                             double* __restrict__ s0, int64_t ldc) {
+  const int64_t npl = (mx + 1) / 2 * 2;  // lanes per coarse row
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int64_t I = i % npl, J = i / npl;
+  const bool live = J < my && I < mx;
+  double v = 0.0;
+  if (live) {
+    const int2 ax = fx[I], ay = fy[J];
+    const double* p = d0 + static_cast<int64_t>(ay.x) * ldd + ax.x;
+    v = mg_tab_restrict_cell(p, ldd, ld2(wx + 4 * I), ld2(wx + 4 * I + 2), ax.y, ld2(wy + 4 * J), ld2(wy + 4 * J + 2),
+                             ay.y);
+  }
+  const double east = __shfl_xor(v, 1);  // every lane of the wave is here: no lane left before
+  if (live && (I & 1) == 0) {
+    double* q = s0 + J * ldc + I;
+    if (I + 1 < mx) {
+      d2 o;
+      o.x = v, o.y = east;
+      st2(q, o);
+    } else {  // the single last coarse column of an odd mx
+      *q = v;
+    }
+  }
+}
+
 }  // namespace gmt
 
 extern "C" int gmt_mg_smooth_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int64_t ld, const double* f,
@@ -314,6 +480,125 @@ extern "C" int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny
     const int64_t nb = (nx * ny + kBlock - 1) / kBlock;
     if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
     mg_prolong_scalar<<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, px, py, e0, lde, u, ld);
+  }
+  GMT_RET_LAUNCH();
+}
+
+// ---- the table-driven transfers ----
+
+extern "C" int gmt_mg_xfer_plan_create(const gmt_mg_xfer_desc* desc, void** plan) {
+  using namespace gmt;
+  if (plan) *plan = nullptr;
+  if (!desc || !plan) return static_cast<int>(hipErrorInvalidValue);
+  // every table on the host first: an index that fails its check is never uploaded
+  MgAxisTab tab[2];
+  for (int a = 0; a < 2; ++a)
+    if (mg_axis_tab_build(desc->n[a], desc->m[a], desc->fo[a], desc->fn[a], desc->co[a], desc->cn[a], &tab[a]) != 0)
+      return static_cast<int>(hipErrorInvalidValue);
+  // one allocation, every table on a 16-B boundary
+  auto pad = [](size_t b) { return (b + 15) / 16 * 16; };
+  size_t off[2][4], bytes = 0;
+  for (int a = 0; a < 2; ++a) {
+    const size_t sz[4] = {tab[a].pq.size() * sizeof(int32_t), tab[a].pt.size() * sizeof(double),
+                          tab[a].rf.size() * sizeof(int32_t), tab[a].rw.size() * sizeof(double)};
+    for (int k = 0; k < 4; ++k) {
+      off[a][k] = bytes;
+      bytes += pad(sz[k]);
+    }
+  }
+  std::vector<char> host(bytes + 16, 0);
+  for (int a = 0; a < 2; ++a) {
+    std::memcpy(host.data() + off[a][0], tab[a].pq.data(), tab[a].pq.size() * sizeof(int32_t));
+    std::memcpy(host.data() + off[a][1], tab[a].pt.data(), tab[a].pt.size() * sizeof(double));
+    std::memcpy(host.data() + off[a][2], tab[a].rf.data(), tab[a].rf.size() * sizeof(int32_t));
+    std::memcpy(host.data() + off[a][3], tab[a].rw.data(), tab[a].rw.size() * sizeof(double));
+  }
+  auto* p = new (std::nothrow) MgXferPlan();
+  if (!p) return static_cast<int>(hipErrorOutOfMemory);
+  hipError_t e = hipMalloc(&p->dev, host.size());
+  if (e == hipSuccess) e = hipMemcpy(p->dev, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (p->dev) (void)hipFree(p->dev);
+    delete p;
+    return static_cast<int>(e);
+  }
+  const char* base = static_cast<const char*>(p->dev);
+  for (int a = 0; a < 2; ++a) {
+    p->fn[a] = desc->fn[a];
+    p->cn[a] = desc->cn[a];
+    p->pq[a] = reinterpret_cast<const int32_t*>(base + off[a][0]);
+    p->pt[a] = reinterpret_cast<const double*>(base + off[a][1]);
+    p->rf[a] = reinterpret_cast<const int2*>(base + off[a][2]);
+    p->rw[a] = reinterpret_cast<const double*>(base + off[a][3]);
+  }
+  *plan = p;
+  return 0;
+}
+
+extern "C" void gmt_mg_xfer_plan_destroy(void* plan) {
+  auto* p = static_cast<gmt::MgXferPlan*>(plan);
+  if (!p) return;
+  if (p->dev) (void)hipFree(p->dev);
+  delete p;
+}
+
+extern "C" int gmt_mg_restrict_tab_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc,
+                                        int64_t ldc) {
+  return gmt::mg_restrict_path(x0, cx0, d, ldd, sc, ldc);
+}
+
+extern "C" int gmt_mg_restrict_tab(const void* plan, int64_t x0, int64_t y0, const double* d, int64_t ldd, double* sc,
+                                   int64_t cx0, int64_t cy0, int64_t ldc, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const auto* p = static_cast<const MgXferPlan*>(plan);
+  if (!p) return static_cast<int>(hipErrorInvalidValue);
+  const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0], my = p->cn[1];
+  if (nx == 0 || ny == 0 || mx == 0 || my == 0) return 0;
+  if (!d || !sc || x0 < kMgTapHalo || y0 < kMgTapHalo || cx0 < 0 || cy0 < 0 || ldd < x0 + nx + kMgTapHalo ||
+      ldc < cx0 + mx)
+    return static_cast<int>(hipErrorInvalidValue);
+  const double* d0 = d + y0 * ldd + x0;
+  double* s0 = sc + cy0 * ldc + cx0;
+  if (mg_restrict_path(x0, cx0, d, ldd, sc, ldc) == GMT_PATH_PT) {
+    const int64_t nb = ((mx + 1) / 2 * 2 * my + kBlock - 1) / kBlock;  // a lane per coarse cell, rows padded to pairs
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    mg_restrict_tab_pt<<<grid_1d(nb), kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0, ldc);
+  } else {
+    const int64_t nb = (mx * my + kBlock - 1) / kBlock;
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    mg_restrict_tab_scalar<<<grid_1d(nb), kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0,
+                                                          ldc);
+  }
+  GMT_RET_LAUNCH();
+}
+
+extern "C" int gmt_mg_prolong_add_tab_path(int64_t x0, const double* e, int64_t lde, const double* u, int64_t ld) {
+  return gmt::mg_prolong_path(x0, e, lde, u, ld);
+}
+
+extern "C" int gmt_mg_prolong_add_tab(const void* plan, int64_t x0, int64_t y0, const double* e, int64_t cx0,
+                                      int64_t cy0, int64_t lde, double* u, int64_t ld, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const auto* p = static_cast<const MgXferPlan*>(plan);
+  if (!p) return static_cast<int>(hipErrorInvalidValue);
+  const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0];
+  if (nx == 0 || ny == 0) return 0;
+  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < kMgRingHalo || cy0 < kMgRingHalo || lde < cx0 + mx + kMgRingHalo ||
+      ld < x0 + nx)
+    return static_cast<int>(hipErrorInvalidValue);
+  const double* e0 = e + cy0 * lde + cx0;
+  double* u0 = u + y0 * ld + x0;
+  if (mg_prolong_path(x0, e, lde, u, ld) == GMT_PATH_PT) {
+    const int64_t nb = ((nx + 1) / 2 * ny + kBlock - 1) / kBlock;
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    mg_prolong_tab_pt<<<grid_1d(nb), kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0, ld);
+  } else {
+    const int64_t nb = (nx * ny + kBlock - 1) / kBlock;
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    mg_prolong_tab_scalar<<<grid_1d(nb), kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0,
+                                                         ld);
   }
   GMT_RET_LAUNCH();
 }

@@ -188,6 +188,12 @@ _SIGS = {
         [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
     ),
     "gmt_mg_prolong_add_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "gmt_mg_xfer_plan_create": (c_int, [c_vp, c_vp]),
+    "gmt_mg_xfer_plan_destroy": (None, [c_vp]),
+    "gmt_mg_restrict_tab": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "gmt_mg_prolong_add_tab": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_mg_restrict_tab_path": (c_int, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "gmt_mg_prolong_add_tab_path": (c_int, [c_i64, c_vp, c_i64, c_vp, c_i64]),
     "gmt_jacobi5_rects": (
         c_int,
         [c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_vp],

@@ -31,6 +31,7 @@ import os
 import numpy as np
 import torch
 
+from . import mg_tab
 from .parallel import dist as gdist
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,7 +103,7 @@ class MgOpts(ctypes.Structure):
     _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
                 ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
                 ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
-                ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int)]
+                ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int)]
 
 
 class MgResult(ctypes.Structure):
@@ -115,6 +116,7 @@ class MgResult(ctypes.Structure):
 
 
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
+COARSEN = {"nested": 0, "any": 1}  # MgOpts::coarsen
 CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
 
@@ -172,6 +174,8 @@ def load(device: str = "cuda") -> ctypes.CDLL:
     lib.gmt_engine_jacobi_cheby.restype = c_int
     lib.gmt_engine_jacobi_mg.argtypes = [vp, ctypes.POINTER(MgOpts), ctypes.POINTER(MgResult)]
     lib.gmt_engine_jacobi_mg.restype = c_int
+    lib.gmt_engine_mg_levels2.argtypes = [ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_int, vp, c_int]
+    lib.gmt_engine_mg_levels2.restype = c_int
     lib.gmt_engine_jacobi_periodic.argtypes = [vp]
     lib.gmt_engine_jacobi_periodic.restype = c_int
     lib.gmt_engine_jacobi_info.argtypes = [vp, ctypes.POINTER(i64)]
@@ -685,15 +689,22 @@ class NativeJacobi:
         return {n: getattr(r, n) for n, _ in ChebyResult._fields_}
 
     def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
-           lag: int = 1, nu: tuple = (2, 2), omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0) -> dict:
+           lag: int = 1, nu: tuple = (2, 2), omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0,
+           coarsen: str = "nested") -> dict:
         """Geometric multigrid V-cycles from the current field
         (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
         ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
         the coarse-level correction, full weighting, bilinear interpolation,
         ``coarse_iters`` Chebyshev iterations from zero on the coarsest level
         (0 = :func:`mg_coarse_iters` of its spectral radius).  Levels are those
-        of :func:`mg_levels` (``max_levels`` 0 = all of them, else >= 2).  An
-        iteration is one cycle; criterion, ``check_every`` (0 = 1), ``lag`` and
+        of :func:`mg_levels` (``max_levels`` 0 = all of them, else >= 2).
+        ``coarsen="nested"`` needs ``nx + 1`` and ``ny + 1`` even on every
+        level; ``coarsen="any"`` takes every lattice size: an axis of ``n``
+        points coarsens to :func:`mg_coarse_extent` points on the same
+        interval, and a level that is not nested transfers by linear
+        interpolation with the weights of :func:`mg_axis_table` and its exact
+        transpose (a level with both extents odd is the nested one, bit for
+        bit).  An iteration is one cycle; criterion, ``check_every`` (0 = 1), ``lag`` and
         the fixed-count mode are :meth:`cg`'s.  The solution replaces the
         current field (the parity flips with an odd ``nu[0] + nu[1]``);
         :meth:`run` afterwards keeps sweeping from it.  The field is bitwise
@@ -723,15 +734,20 @@ class NativeJacobi:
             raise ValueError(f"omega must be in (0, 1], got {omega!r}")
         if int(max_levels) < 0 or int(max_levels) == 1 or int(coarse_iters) < 0:
             raise ValueError("max_levels must be 0 or >= 2 and coarse_iters >= 0")
+        if coarsen not in COARSEN:
+            raise ValueError(f"coarsen must be one of {sorted(COARSEN)}, got {coarsen!r}")
         o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
-                   nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters))
+                   nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters),
+                   coarsen=COARSEN[coarsen])
         r = MgResult()
         rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
         if rc == 2:
             raise ValueError("mg needs Dirichlet sides: I - J is singular on a periodic axis")
         if rc in (3, 4):
-            raise ValueError("mg: no coarse level: " + ("nx + 1 and ny + 1 must be even" if rc == 3 else
-                                                        "a rank of the process grid would own no coarse point"))
+            raise ValueError("mg: no coarse level: " + (
+                "nx + 1 and ny + 1 must be even" if rc == 3 else
+                "a rank of the process grid would own no coarse point" if coarsen == "nested" else
+                "the extents are too small or a rank of the process grid would own no coarse point"))
         if rc:
             raise ValueError("gmt_engine_jacobi_mg rejected its options")
         return {n: getattr(r, n) for n, _ in MgResult._fields_}
@@ -1068,24 +1084,79 @@ def mg_coarse_iters(rho: float) -> int:
     return k
 
 
-def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0) -> list:
+def mg_coarse_extent(n: int) -> int:
+    """Coarse points of an axis of ``n`` fine ones under ``coarsen="any"``:
+    ``(n-1)/2`` for odd ``n`` (the nested rule, spacing 2), ``n/2 - 1`` for
+    even ``n`` (spacing ``(n+1)/(n/2)``)."""
+    return mg_tab.coarse_extent(n)
+
+
+def mg_axis_table(n: int, m: int):
+    """The interpolation table of an axis with ``n`` fine and ``m`` coarse
+    interior points on the same interval, the definition the engine, both
+    kernel backends and :func:`serial_mg` share: arrays ``(q, t, r)`` whose
+    entry ``i - 1`` belongs to fine point ``i`` (1-based),
+    ``q, r = divmod(i*(m+1), n+1)`` in 64-bit integers and ``t = r/(n+1)`` by
+    one fp64 division.  Fine ``i`` lies between coarse ``q`` and ``q + 1``
+    (0 and m + 1 are the ring) with the weights ``1.0 - t`` and ``t``;
+    :func:`mg_tab.axis_taps` is the transpose."""
+    return mg_tab.axis_table(n, m)
+
+
+def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0, coarsen: str = "nested") -> list:
     """The level table of :meth:`NativeJacobi.mg`: global ``(ny, nx)`` of every
-    level, the fine one first.  A level has the coarser level
-    ``((ny-1)/2, (nx-1)/2)`` while ``nx + 1`` and ``ny + 1`` are even, every
-    rank of the ``dims = (py, px)`` grid keeps a coarse row and column (a rank
-    owning fine columns ``[ox, ox+nx)`` owns coarse columns
-    ``[ox/2, (ox+nx)/2)``) and ``max_levels`` (0: no limit) is not reached."""
+    level, the fine one first.  ``coarsen="nested"``: a level has the coarser
+    level ``((ny-1)/2, (nx-1)/2)`` while ``nx + 1`` and ``ny + 1`` are even,
+    every rank of the ``dims = (py, px)`` grid keeps a coarse row and column (a
+    rank owning fine columns ``[ox, ox+nx)`` owns coarse columns
+    ``[ox/2, (ox+nx)/2)``) and ``max_levels`` (0: no limit) is not reached.
+    ``coarsen="any"``: each axis goes to :func:`mg_coarse_extent` points while
+    both stay >= 1; coarse point ``J`` of an axis belongs to the rank that owns
+    fine cell ``J*(n+1) // (m+1)``; every rank keeps a coarse row and column;
+    and on a level with an even extent every rank's tables must pass the
+    checks of the transfer plan (3 or 4 taps, taps within 2 cells and
+    interpolated coarse cells within 1 of the share) and a rank with a
+    neighbour on an axis must have 2 cells there."""
+    if coarsen not in COARSEN:
+        raise ValueError(f"coarsen must be one of {sorted(COARSEN)}, got {coarsen!r}")
+
     def bounds(n, p):
         base, rem = divmod(n, p)
         return [i * base + min(i, rem) for i in range(p)] + [n]
 
+    def any_axis(n, m, b, tables):
+        cb = [int(v) for v in mg_tab.coarse_bound(n, m, b)]
+        if any(c1 <= c0 for c0, c1 in zip(cb, cb[1:])):
+            return None
+        if tables:
+            for k in range(len(b) - 1):
+                if len(b) > 2 and b[k + 1] - b[k] < mg_tab.TAP_HALO:
+                    return None
+                try:
+                    mg_tab.region_tables(n, m, b[k], b[k + 1] - b[k], cb[k], cb[k + 1] - cb[k])
+                except ValueError:
+                    return None
+        return cb
+
     by, bx = bounds(ny, int(dims[0])), bounds(nx, int(dims[1]))
     out = [(ny, nx)]
-    while (max_levels == 0 or len(out) < max_levels) and ny % 2 == 1 and nx % 2 == 1:
-        by, bx = [b // 2 for b in by], [b // 2 for b in bx]
-        if any(b1 <= b0 for b in (by, bx) for b0, b1 in zip(b, b[1:])):
-            break
-        ny, nx = (ny - 1) // 2, (nx - 1) // 2
+    while max_levels == 0 or len(out) < max_levels:
+        if coarsen == "nested":
+            if ny % 2 == 0 or nx % 2 == 0:
+                break
+            by, bx = [b // 2 for b in by], [b // 2 for b in bx]
+            if any(b1 <= b0 for b in (by, bx) for b0, b1 in zip(b, b[1:])):
+                break
+            ny, nx = (ny - 1) // 2, (nx - 1) // 2
+        else:
+            my, mx = mg_tab.coarse_extent(ny), mg_tab.coarse_extent(nx)
+            if my < 1 or mx < 1:
+                break
+            tables = ny % 2 == 0 or nx % 2 == 0
+            cy, cx = any_axis(ny, my, by, tables), any_axis(nx, mx, bx, tables)
+            if cy is None or cx is None:
+                break
+            (ny, by), (nx, bx) = (my, cy), (mx, cx)
         out.append((ny, nx))
     return out
 
@@ -1093,12 +1164,13 @@ def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0) -> li
 def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int = 0,
               source: "str | np.ndarray | None" = None, source_amp: float = 1.0, nu: tuple = (2, 2),
               omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0, coarse_rho: "float | None" = None,
-              keep=None, start: "np.ndarray | None" = None):
+              keep=None, start: "np.ndarray | None" = None, coarsen: str = "nested"):
     """NumPy definition of :meth:`NativeJacobi.mg` on the whole Dirichlet
     problem: ``cycles`` V-cycles from the engine's initial field, every cell in
     the kernels' operation order (ops/reference.py ``mg_smooth``,
-    ``mg_restrict``, ``mg_prolong_add``; the coarsest level as
-    :func:`serial_cheby` from zero) — bitwise the engine's field.
+    ``mg_restrict``, ``mg_prolong_add``, and with ``coarsen="any"`` on a level
+    with an even extent ``mg_restrict_tab``, ``mg_prolong_add_tab``; the
+    coarsest level as :func:`serial_cheby` from zero) — bitwise the engine's field.
     ``coarse_rho``: the coarsest level's spectral radius (default
     :func:`cheby_rho`; the engine reports the value it used).  ``start``: an
     ny x nx interior to start from inside the initial field's ring, as a call
@@ -1109,9 +1181,10 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
     after k cycles."""
     from .ops import reference as ref
 
-    levels = mg_levels(ny, nx, (1, 1), max_levels)
+    levels = mg_levels(ny, nx, (1, 1), max_levels, coarsen)
     if len(levels) < 2:
-        raise ValueError("mg: no coarse level: nx + 1 and ny + 1 must be even")
+        raise ValueError("mg: no coarse level: " + ("nx + 1 and ny + 1 must be even" if coarsen == "nested" else
+                                                    "the extents leave no coarse point"))
     nu1, nu2 = (int(v) for v in nu)
     rho = cheby_rho(*levels[-1]) if coarse_rho is None else float(coarse_rho)
     citers = int(coarse_iters) or mg_coarse_iters(rho)
@@ -1121,7 +1194,7 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
         u0[1:-1, 1:-1] = start
     U = [[u0, u0.copy()]] + [[np.zeros((m + 2, n + 2)), np.zeros((m + 2, n + 2))] for m, n in levels[1:]]
     S = [None] + [np.zeros((m + 2, n + 2)) for m, n in levels[1:]]
-    D = [np.zeros((m + 2, n + 2)) for m, n in levels]
+    D = [np.zeros((m + 4, n + 4)) for m, n in levels]  # room for the 2-wide ring the general restriction allows
     if source is not None:
         S[0] = np.zeros((ny + 2, nx + 2))
         S[0][1:-1, 1:-1] = source_field(ny, nx, source, seed, source_amp)
@@ -1148,11 +1221,20 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
             ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
             cur ^= 1
         a = u[cur]
-        D[lv][1:-1, 1:-1] = sweep(a, f) - a[1:-1, 1:-1]
-        ref.mg_restrict(D[lv], S[lv + 1], 0.25, 1, n, 1, m, 1, 1, 1, 1)
+        D[lv][2:-2, 2:-2] = sweep(a, f) - a[1:-1, 1:-1]
+        tab = m % 2 == 0 or n % 2 == 0  # not nested: the table-driven transfers over the whole level
+        (mc, nc) = levels[lv + 1]
+        xaxis, yaxis = (n, nc, 0, n, 0, nc), (m, mc, 0, m, 0, mc)
+        if tab:
+            ref.mg_restrict_tab(D[lv], S[lv + 1], xaxis, yaxis, 2, 2, 1, 1)
+        else:
+            ref.mg_restrict(D[lv][1:-1, 1:-1], S[lv + 1], 0.25, 1, n, 1, m, 1, 1, 1, 1)
         U[lv + 1][0][...] = 0.0
         c = cycle(lv + 1, 0)
-        ref.mg_prolong_add(U[lv + 1][c], a, 1, n, 1, m, 1, 1, 1, 1)
+        if tab:
+            ref.mg_prolong_add_tab(U[lv + 1][c], a, xaxis, yaxis, 1, 1, 1, 1)
+        else:
+            ref.mg_prolong_add(U[lv + 1][c], a, 1, n, 1, m, 1, 1, 1, 1)
         for _ in range(nu2):
             ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
             cur ^= 1

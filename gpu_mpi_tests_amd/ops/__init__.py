@@ -8,7 +8,9 @@ and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
 its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
 ``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``,
 the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
-``mg_prolong_add`` and ``jacobi5tb`` (K fused sweeps per memory pass).
+``mg_prolong_add``, their table-driven forms for levels that are not nested
+``mg_restrict_tab`` / ``mg_prolong_add_tab``, and ``jacobi5tb`` (K fused sweeps
+per memory pass).
 """
 from .kernels import (  # noqa: F401
     abs_max,
@@ -42,8 +44,12 @@ from .kernels import (  # noqa: F401
     jacobi5_resid_path,
     mg_prolong_add,
     mg_prolong_add_path,
+    mg_prolong_add_tab,
+    mg_prolong_add_tab_path,
     mg_restrict,
     mg_restrict_path,
+    mg_restrict_tab,
+    mg_restrict_tab_path,
     mg_smooth,
     mg_smooth_path,
     jacobi5xk,

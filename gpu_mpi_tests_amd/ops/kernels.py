@@ -664,6 +664,84 @@ def mg_prolong_add_path(e: torch.Tensor, u: torch.Tensor, region: tuple[int, int
                                                      u.stride(0)))
 
 
+class MgXferDesc(ctypes.Structure):
+    """gmt_mg_xfer_desc (csrc/include/gmt/kernels.h): index 0 of each pair is x, 1 is y."""
+    _fields_ = [(k, ctypes.c_int64 * 2) for k in ("n", "m", "fo", "fn", "co", "cn")]
+
+
+class _XferPlan:
+    """A gmt_mg_xfer_plan of one call: built and checked on the host, destroyed
+    once the launch that used it has finished."""
+
+    def __init__(self, xaxis, yaxis, what: str):
+        d = MgXferDesc()
+        for k, (vx, vy) in zip(("n", "m", "fo", "fn", "co", "cn"), zip(xaxis, yaxis)):
+            getattr(d, k)[0], getattr(d, k)[1] = int(vx), int(vy)
+        self.h = ctypes.c_void_p()
+        if _native.lib().gmt_mg_xfer_plan_create(ctypes.byref(d), ctypes.byref(self.h)) or not self.h:
+            raise ValueError(f"{what}: gmt_mg_xfer_plan_create refused the description {tuple(xaxis)}, {tuple(yaxis)}")
+
+    def __enter__(self):
+        return self.h
+
+    def __exit__(self, *exc):
+        torch.cuda.synchronize()
+        _native.lib().gmt_mg_xfer_plan_destroy(self.h)
+
+
+def mg_restrict_tab(d: torch.Tensor, sc: torch.Tensor, xaxis: tuple, yaxis: tuple, origin: tuple[int, int],
+                    coarse: tuple[int, int]) -> torch.Tensor:
+    """``sc = P^T d`` between two levels that are not nested
+    (gmt_mg_restrict_tab): ``xaxis`` / ``yaxis`` = ``(n, m, fo, fn, co, cn)``,
+    the global fine and coarse point counts of the axis and the region's fine
+    cells ``fo+1 .. fo+fn`` and coarse cells ``co+1 .. co+cn``; the fine region
+    sits at ``origin = (x0, y0)`` of ``d``, the coarse one at
+    ``coarse = (cx0, cy0)`` of ``sc``.  The call builds its own plan
+    (gmt_mg_xfer_plan_create checks every table index on the host); ValueError
+    where that refuses.  Bitwise :func:`reference.mg_restrict_tab`.  Returns ``sc``."""
+    _check2d(d, "mg_restrict_tab.d")
+    _check2d(sc, "mg_restrict_tab.sc")
+    (x0, y0), (cx0, cy0) = (int(t) for t in origin), (int(t) for t in coarse)
+    if not _is_dev(sc):
+        return ref.mg_restrict_tab(d, sc, xaxis, yaxis, x0, y0, cx0, cy0)
+    with _XferPlan(xaxis, yaxis, "mg_restrict_tab") as plan:
+        _native.check(_native.lib().gmt_mg_restrict_tab(plan, x0, y0, d.data_ptr(), d.stride(0), sc.data_ptr(), cx0,
+                                                        cy0, sc.stride(0), _stream(sc)), "gmt_mg_restrict_tab")
+    return sc
+
+
+def mg_restrict_tab_path(d: torch.Tensor, sc: torch.Tensor, origin: tuple[int, int], coarse: tuple[int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`mg_restrict_tab` would launch (no launch)."""
+    return int(_native.lib().gmt_mg_restrict_tab_path(int(origin[0]), int(coarse[0]), d.data_ptr(), d.stride(0),
+                                                      sc.data_ptr(), sc.stride(0)))
+
+
+def mg_prolong_add_tab(e: torch.Tensor, u: torch.Tensor, xaxis: tuple, yaxis: tuple, origin: tuple[int, int],
+                       coarse: tuple[int, int]) -> torch.Tensor:
+    """``u += P e``, P linear interpolation between two levels that are not
+    nested (gmt_mg_prolong_add_tab); arguments as for :func:`mg_restrict_tab`
+    with ``e`` the coarse field.  Bitwise :func:`reference.mg_prolong_add_tab`.
+    ``e`` and ``u`` must not share storage.  Returns ``u``."""
+    _check2d(e, "mg_prolong_add_tab.e")
+    _check2d(u, "mg_prolong_add_tab.u")
+    if _overlap(e, u):
+        raise ValueError("mg_prolong_add_tab: e and u must not share storage")
+    (x0, y0), (cx0, cy0) = (int(t) for t in origin), (int(t) for t in coarse)
+    if not _is_dev(u):
+        return ref.mg_prolong_add_tab(e, u, xaxis, yaxis, x0, y0, cx0, cy0)
+    with _XferPlan(xaxis, yaxis, "mg_prolong_add_tab") as plan:
+        _native.check(_native.lib().gmt_mg_prolong_add_tab(plan, x0, y0, e.data_ptr(), cx0, cy0, e.stride(0),
+                                                           u.data_ptr(), u.stride(0), _stream(u)),
+                      "gmt_mg_prolong_add_tab")
+    return u
+
+
+def mg_prolong_add_tab_path(e: torch.Tensor, u: torch.Tensor, origin: tuple[int, int]) -> int:
+    """PATH_PT or PATH_SCALAR: the kernel :func:`mg_prolong_add_tab` would launch (no launch)."""
+    return int(_native.lib().gmt_mg_prolong_add_tab_path(int(origin[0]), e.data_ptr(), e.stride(0), u.data_ptr(),
+                                                         u.stride(0)))
+
+
 def jacobi5_rects(u: torch.Tensor, un: torch.Tensor, rects: Sequence[tuple[int, int, int, int]],
                   f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 0.0) -> None:
     """Sweep up to 4 rectangles (the boundary frame of an overlapped step) in one launch."""

@@ -7,6 +7,7 @@ kernels where it matters for bitwise distributed-vs-serial checks.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 # 4th-order central first-derivative coefficients (mpi_stencil2d_gt.cc:75-76).
@@ -251,6 +252,69 @@ def mg_prolong_add(e, u, x0: int, nx: int, y0: int, ny: int, px: int, py: int, c
     s = sel(fy(ybt), fx(xbt))
     if s:
         u[s] = u[s] + 0.25 * ((at(Ybt, Xbt) + at(Ybt, Xbt, 0, 1)) + (at(Ybt, Xbt, 1, 0) + at(Ybt, Xbt, 1, 1)))
+    return u
+
+
+def _np_view(a):
+    """A NumPy view of a CPU tensor's storage (the array itself for NumPy)."""
+    return a.numpy() if isinstance(a, torch.Tensor) else a
+
+
+def mg_restrict_tab(d, sc, xaxis, yaxis, x0: int, y0: int, cx0: int, cy0: int):
+    """gmt_mg_restrict_tab: ``sc = P^T d`` between two levels that are not
+    nested.  ``xaxis`` / ``yaxis`` = ``(n, m, fo, fn, co, cn)``: the global
+    fine and coarse point counts and the region's fine and coarse cells
+    (mg_tab.region_tables).  Per coarse cell, over its 3 or 4 taps per axis:
+    ``h_k = ((wx0*d0 + wx1*d1) + wx2*d2) [+ wx3*d3]`` per tapped row, then
+    ``s = ((wy0*h0 + wy1*h1) + wy2*h2) [+ wy3*h3]``; only real taps are read."""
+    from .. import mg_tab
+
+    tx, ty = mg_tab.region_tables(*xaxis), mg_tab.region_tables(*yaxis)
+    D, S = _np_view(d), _np_view(sc)
+    mx, my = len(tx["rf"]), len(ty["rf"])
+    if mx == 0 or my == 0 or int(xaxis[3]) == 0 or int(yaxis[3]) == 0:
+        return sc
+    if x0 < mg_tab.TAP_HALO or y0 < mg_tab.TAP_HALO or cx0 < 0 or cy0 < 0:
+        raise ValueError("mg_restrict_tab: x0 and y0 >= 2, cx0 and cy0 >= 0")
+
+    def gather(A, f, c, w, axis_first):
+        """((w0*A0 + w1*A1) + w2*A2) [+ w3*A3] over the taps f .. f+c-1 of each coarse index."""
+        take = (lambda i: A[i]) if axis_first else (lambda i: A[:, i])
+        shape = (lambda v: v[:, None]) if axis_first else (lambda v: v[None, :])
+        out = (shape(w[:, 0]) * take(f) + shape(w[:, 1]) * take(f + 1)) + shape(w[:, 2]) * take(f + 2)
+        four = c == 4
+        if four.any():
+            t3 = shape(w[:, 3]) * take(f + np.where(four, 3, 2))  # a column with 3 taps re-reads its third
+            out = np.where(shape(four), out + t3, out)
+        return out
+
+    r0, r1 = int(ty["rf"].min()), int((ty["rf"] + ty["rc"]).max())  # the tapped fine rows, region-relative
+    H = gather(D[y0 + r0:y0 + r1], x0 + tx["rf"], tx["rc"], tx["rw"], False)
+    S[cy0:cy0 + my, cx0:cx0 + mx] = gather(H, ty["rf"] - r0, ty["rc"], ty["rw"], True)
+    return sc
+
+
+def mg_prolong_add_tab(e, u, xaxis, yaxis, x0: int, y0: int, cx0: int, cy0: int):
+    """gmt_mg_prolong_add_tab: ``u += P e``; axes as for :func:`mg_restrict_tab`.
+    Per fine cell with ``(I, tx)`` of its column and ``(J, ty)`` of its row,
+    ``w0 = 1.0 - t``: ``bot = w0x*e[J][I] + tx*e[J][I+1]``,
+    ``top = w0x*e[J+1][I] + tx*e[J+1][I+1]``, ``v = w0y*bot + ty*top``, ``u = u + v``."""
+    from .. import mg_tab
+
+    tx, ty = mg_tab.region_tables(*xaxis), mg_tab.region_tables(*yaxis)
+    E, U = _np_view(e), _np_view(u)
+    nx, ny = len(tx["pq"]), len(ty["pq"])
+    if nx == 0 or ny == 0:
+        return u
+    if x0 < 1 or y0 < 1 or cx0 < mg_tab.RING_HALO or cy0 < mg_tab.RING_HALO:
+        raise ValueError("mg_prolong_add_tab: x0, y0, cx0 and cy0 >= 1")
+    I, J = (cx0 + tx["pq"])[None, :], (cy0 + ty["pq"])[:, None]
+    t1x, t1y = tx["pt"][None, :], ty["pt"][:, None]
+    w0x, w0y = 1.0 - t1x, 1.0 - t1y
+    bot = w0x * E[J, I] + t1x * E[J, I + 1]
+    top = w0x * E[J + 1, I] + t1x * E[J + 1, I + 1]
+    v = w0y * bot + t1y * top
+    U[y0:y0 + ny, x0:x0 + nx] = U[y0:y0 + ny, x0:x0 + nx] + v
     return u
 
 
