@@ -23,7 +23,9 @@
 //      --only=mg [--reps=5] [--mg-n=N]: the kernels of a multigrid cycle
 //      (gmt_mg_smooth 16 B/fine point, 24 with f, gmt_mg_restrict 10,
 //      gmt_mg_prolong_add 18) on N x N (default 8191; an even N times them at
-//      N - 1 and the table-driven transfers of coarsen = any at N), as --only=cg
+//      N - 1 and the table-driven transfers of coarsen = any at N), as --only=cg;
+//      then the fused smoother gmt_mg_smooth_k for k = 2, 3, 4 without and with
+//      f, compared bitwise with k single sweeps and timed beside them and DAXPY
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -568,6 +570,69 @@ int main(int argc, char** argv) {
     for (int k = 0; k < 4; ++k) {
       if (k == 3) GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
       best[k] = compare(name[k], k, kernel[k], daxpy, bytes[k], n);
+    }
+    {
+      // the fused smoother (gmt_mg_smooth_k, mask 0) for k = 2, 3, 4 without and with f: first compared
+      // bitwise with k single sweeps between two buffers that hold u's ring, then timed beside those k
+      // launches and DAXPY in the order A B C C B A.  GB/s from the same compulsory 16 (24) bytes a point.
+      Buffer<double> w(elems, GMT_SPACE_DEVICE), x(elems, GMT_SPACE_DEVICE);
+      Buffer<double> dws(static_cast<size_t>(2 * gmt_diff_sq_workspace(n, n)) + 2, GMT_SPACE_DEVICE);
+      GMT_CHECK("memset", gmt_rt_memset_async(w.data(), 0, w.bytes(), s));
+      for (int k = 2; k <= GMT_MG_MAX_FUSE; ++k)
+        for (int wf = 0; wf < 2; ++wf) {
+          // the same field and ring in the three buffers (DAXPY below updates u)
+          for (double* b : {u.data(), v.data(), x.data()})
+            GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, b, ld, s));
+          const double* fp = wf ? f.data() : nullptr;
+          const int64_t ldf = wf ? ld : 0;
+          const double c1 = wf ? 1.0 : 0.0, bpp = wf ? 24.0 : 16.0;
+          char nm[32], nms[32], nmd[32];
+          std::snprintf(nm, sizeof(nm), "mg_smooth_k%d%s", k, wf ? "_f" : "");
+          std::snprintf(nms, sizeof(nms), "mg_smooth_x%d%s", k, wf ? "_f" : "");
+          std::snprintf(nmd, sizeof(nmd), "daxpy_k%d%s", k, wf ? "_f" : "");
+          const std::function<void()> fused = [&] {
+            GMT_CHECK(nm, gmt_mg_smooth_k(k, xo, n, 1, n, 0, u.data(), ld, fp, ldf, 0.25, c1, 0.8, w.data(), ld, s));
+          };
+          // u -> v -> x -> v ...: the result is in v for an odd k, in x for an even one
+          const std::function<void()> singles = [&] {
+            const double* src = u.data();
+            for (int j = 0; j < k; ++j) {
+              double* dst = j % 2 == 0 ? v.data() : x.data();
+              GMT_CHECK(nms, gmt_mg_smooth(xo, n, 1, n, src, ld, fp, ldf, 0.25, c1, 0.8, dst, ld, s));
+              src = dst;
+            }
+          };
+          int64_t segk = 0;
+          const int pk = gmt_mg_smooth_k_path(k, xo, n, n, 0, u.data(), ld, fp, ldf, w.data(), ld, &segk);
+          fused();
+          singles();
+          const double* last = k % 2 ? v.data() : x.data();
+          GMT_CHECK("diff", gmt_diff_bits(n, n, w.data() + ld + xo, ld, last + ld + xo, ld, dws.data(), dws.data() + 2, s));
+          double dres[2] = {-1.0, -1.0};
+          GMT_CHECK("D2H", gmt_rt_memcpy_async(dres, dws.data(), sizeof(dres), s));
+          GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+          std::printf("mg %lldx%lld  %s path %d (%lld rows per segment), %s bitwise %d x mg_smooth: %s\n", (long long)n,
+                      (long long)n, nm, pk, (long long)segk, nm, k, dres[1] == 0.0 ? "yes" : "NO");
+          if (dres[1] != 0.0) return 1;
+          Stats st[3];
+          const int order[6] = {0, 1, 2, 2, 1, 0};
+          const std::function<void()>* fn[3] = {&fused, &singles, &daxpy};
+          const char* label[3] = {nm, nms, "daxpy"};
+          for (int rep = 0; rep < reps; ++rep)
+            for (int o = 0; o < 6; ++o) {
+              const double ms = time_ms(s, iters, *fn[order[o]]);
+              st[order[o]].add(ms);
+              std::printf("mg %lldx%lld rep %d  %-18s %9.4f ms\n", (long long)n, (long long)n, rep, label[order[o]], ms);
+            }
+          char shape[64];
+          std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+          report(nm, 0, shape, st[0].min(), bpp * n * n);
+          report(nms, 0, shape, st[1].min(), bpp * k * n * n);
+          report(nmd, 0, shape, st[2].min(), 24.0 * n * n);
+          std::printf("mg %lldx%lld  %s ms / %d x mg_smooth ms = %.4f, GB/s / daxpy GB/s = %.4f  (best of %d)\n",
+                      (long long)n, (long long)n, nm, k, st[0].min() / st[1].min(),
+                      (bpp / st[0].min()) / (24.0 / st[2].min()), reps);
+        }
     }
     if (nt % 2 == 0) {
       // the general transfers on nt x nt: d with room for a 2-wide ring (interior origin (8, 2)), the same

@@ -58,7 +58,7 @@
 //                           converges more slowly, an under-estimate can stagnate).  --check runs
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
-//   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any]
+//   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any] [--fuse=K]
 //                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
 //                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
 //                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
@@ -66,7 +66,9 @@
 //                           (default 2,2), W their damping (default 0.8), N the number of levels
 //                           (default: all), C the Chebyshev iterations on the coarsest level
 //                           (default: from its spectral radius).  --check runs the same number of
-//                           serial cycles and compares within 1e-10 * max|u0|
+//                           serial cycles and compares within 1e-10 * max|u0|.  K (0, or 2..4) runs
+//                           up to K sweeps of a smoothing run in one memory pass (MgOpts::fuse) for
+//                           the same bits
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -522,6 +524,12 @@ int main(int argc, char** argv) {
       MPI_Abort(MPI_COMM_WORLD, 1);
     }
     mo.coarsen = coarsen == "any" ? 1 : 0;
+    mo.fuse = static_cast<int>(cli.geti("fuse", 0));
+    if (mo.fuse != 0 && (mo.fuse < 2 || mo.fuse > GMT_MG_MAX_FUSE)) {
+      if (rank == 0) std::printf("ERROR: --fuse must be 0 or 2..%d\n", GMT_MG_MAX_FUSE);
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
     if (!nu_ok || mo.nu1 < 0 || mo.nu2 < 0 || mo.nu1 + mo.nu2 == 0 || !(mo.omega > 0 && mo.omega <= 1) ||
         mo.max_levels < 0 || mo.max_levels == 1 || mo.coarse_iters < 0) {
       if (rank == 0)
@@ -814,6 +822,9 @@ int main(int argc, char** argv) {
                     (long long)mr.coarse_ny, (long long)mr.coarse_nx, mr.coarse_iters, mr.coarse_rho);
         std::printf("cycle     = V(%d,%d), omega %g\n", mo.nu1, mo.nu2, mo.omega);
         std::printf("coarsen   = %s\n", mo.coarsen ? "any" : "nested");
+        if (mo.fuse)
+          std::printf("fuse      = %d (fine level %d, %d of %d levels fused)\n", mr.fuse, mr.fuse_fine, mr.fuse_levels,
+                      mr.levels - 1);
       }
       if (cg_fixed)
         std::printf("solve     = fixed count, %s norm, check every %d %ss\n", co.norm ? "max" : "l2",
@@ -882,7 +893,8 @@ int main(int argc, char** argv) {
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
     if (mg_mode)
       j.add("solver", "multigrid").add("coarsen", mo.coarsen ? "any" : "nested").add("levels", mr.levels)
-          .add("cycles", mr.iters)
+          .add("cycles", mr.iters).add("fuse", mr.fuse).add("fuse_fine", mr.fuse_fine)
+          .add("fuse_levels", mr.fuse_levels)
           .add("residual_cycles", mr.residual_iters).add("checks", mr.checks).add("converged", mr.converged != 0)
           .add("solve_ms", solve_ms).add("r0", mr.r0).add("residual_max", mr.residual_max);
     else if (cg_mode)

@@ -303,6 +303,7 @@ int JacobiSolver::set_source(const double* host) {
     GMT_CHECK("source sync", gmt_rt_stream_synchronize(s_));
   }
   if (ks_ > 1 && !exact_ && !source_bound_ok(m, ks_)) return 3;
+  f_ring_ = 0;
   GMT_CHECK("source H2D", gmt_rt_memcpy2d_async(f_.data() + xo_ + yo_ * ld_, ld_ * sizeof(double), host,
                                                 nx_ * sizeof(double), nx_ * sizeof(double), ny_, s_));
   GMT_CHECK("source sync", gmt_rt_stream_synchronize(s_));
@@ -1428,6 +1429,32 @@ std::vector<std::pair<int64_t, int64_t>> mg_level_table(int64_t ny, int64_t nx, 
   return mg_level_table(ny, nx, py, px, max_levels, 0);
 }
 
+namespace {
+// the depth of one level from the smallest shares of its axes (0: the axis has one rank)
+int mg_fuse_depth(int fuse, int64_t min_ny, int64_t min_nx, bool fine, int ranks, int ghost) {
+  int64_t d = fuse < 1 ? 1 : fuse;
+  if (min_ny > 0) d = std::min(d, min_ny);
+  if (min_nx > 0) d = std::min(d, min_nx);
+  if (fine && ranks > 1) d = std::min<int64_t>(d, ghost);
+  return static_cast<int>(std::max<int64_t>(d, 1));
+}
+int64_t mg_min_share(const std::vector<int64_t>& b) {
+  if (b.size() <= 2) return 0;
+  int64_t m = b[1] - b[0];
+  for (size_t k = 1; k + 1 < b.size(); ++k) m = std::min(m, b[k + 1] - b[k]);
+  return m;
+}
+}  // namespace
+
+std::vector<int> mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
+                                int coarsen) {
+  const auto shapes = mg_hierarchy(ny, nx, py, px, max_levels, coarsen);
+  std::vector<int> out;
+  for (size_t l = 0; l + 1 < shapes.size(); ++l)
+    out.push_back(mg_fuse_depth(fuse, mg_min_share(shapes[l].by), mg_min_share(shapes[l].bx), l == 0, py * px, ghost));
+  return out;
+}
+
 std::unique_ptr<Halo2D> JacobiSolver::ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny,
                                                 int64_t ld, bool corners, int width) {
   Neighbors nb = nb_;
@@ -1437,9 +1464,11 @@ std::unique_ptr<Halo2D> JacobiSolver::ring_halo(double* field, int64_t xo, int64
 }
 
 // Every level the problem has under mgc_ (mg_hierarchy without a limit); a
-// call with max_levels uses the first of them.
+// call with max_levels uses the first of them.  The hierarchy of fused calls
+// (mgh_ >= 2) gives its coarse levels GMT_MG_MAX_FUSE ghost rows and columns.
 void JacobiSolver::mg_setup() {
-  std::vector<MgLevel>& mg = mg_[mgc_];
+  std::vector<MgLevel>& mg = mg_[mgh_];
+  const bool wide = mgh_ >= 2;
   if (!mg.empty()) return;
   watchdog_kick("jacobi: mg set-up");
   cheby_setup();
@@ -1455,6 +1484,7 @@ void JacobiSolver::mg_setup() {
     MgLevel& L = mg[l];
     L.ny_g = shapes[l].ny;
     L.nx_g = shapes[l].nx;
+    L.min_ny = mg_min_share(shapes[l].by), L.min_nx = mg_min_share(shapes[l].bx);
     size_t elems = static_cast<size_t>(ld_) * (ny_ + 2 * g_);
     if (l == 0) {
       L.nx = nx_, L.ny = ny_, L.ox = ox_, L.oy = oy_;
@@ -1462,8 +1492,9 @@ void JacobiSolver::mg_setup() {
     } else {
       L.ox = shapes[l].bx[cx], L.nx = shapes[l].bx[cx + 1] - L.ox;
       L.oy = shapes[l].by[cy], L.ny = shapes[l].by[cy + 1] - L.oy;
-      L.xo = 8, L.yo = 1, L.ld = round_up(L.xo + L.nx + 1, 64);
-      elems = static_cast<size_t>(L.ld) * (L.ny + 2);
+      const int64_t gh = wide ? GMT_MG_MAX_FUSE : 1;
+      L.xo = 8, L.yo = gh, L.ld = round_up(L.xo + L.nx + gh, 64);
+      elems = static_cast<size_t>(L.ld) * (L.ny + 2 * gh);
       for (int b = 0; b < 2; ++b) {
         L.u[b] = zeroed(elems);
         L.up[b] = L.u[b].data();
@@ -1503,7 +1534,7 @@ void JacobiSolver::mg_setup() {
 }
 
 void JacobiSolver::mg_ring(int l) {
-  MgLevel& L = mg_[mgc_][l];
+  MgLevel& L = mg_[mgh_][l];
   if (L.ring) return;
   Halo2D& h = l == 0 ? *cheby_halo_[L.cur] : *L.hu[L.cur];
   if (h.active()) {
@@ -1513,8 +1544,70 @@ void JacobiSolver::mg_ring(int l) {
   L.ring = true;
 }
 
+// The depth of every smoothing level of this call (mg_fuse_depths' rule on the
+// shares mg_setup kept) and, on first use, the wide halo plans it needs: of
+// either buffer at the level's depth, of the source one cell narrower.  Level
+// 0's source ring is exchanged here, once per source.
+void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
+  std::vector<MgLevel>& mg = mg_[mgh_];
+  for (int l = 0; l < static_cast<int>(mg.size()); ++l) {
+    MgLevel& L = mg[l];
+    L.depth = l + 1 < levels ? mg_fuse_depth(o.fuse, L.min_ny, L.min_nx, l == 0, t_.size(), g_) : 1;
+    if (L.depth < 2 || t_.size() == 1) continue;
+    const int d = L.depth;
+    for (int b = 0; b < 2; ++b) {
+      if (L.hk[b][d] && L.hk_field[b] == L.up[b]) continue;
+      L.hk[b][d] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true, d);
+      L.hk_field[b] = L.up[b];
+    }
+    if (L.sp && !L.hs[d - 1])
+      L.hs[d - 1] = ring_halo(const_cast<double*>(L.sp), L.xo, L.yo, L.nx, L.ny, L.ld, true, d - 1);
+  }
+  MgLevel& F = mg[0];
+  if (F.depth >= 2 && F.sp && t_.size() > 1 && f_ring_ < F.depth - 1) {
+    Halo2D& h = *F.hs[F.depth - 1];
+    if (h.active()) {
+      h.start(s_);
+      h.finish(s_);
+    }
+    f_ring_ = F.depth - 1;
+  }
+}
+
+// n sweeps of the smoother on level l: chunks of min(n, depth); a chunk of two
+// or more is one depth-wide exchange with corners and one gmt_mg_smooth_k
+void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o) {
+  MgLevel& L = mg_[mgh_][l];
+  const int64_t ldf = L.sp ? L.ld : 0;
+  const double c1 = L.sp ? 1.0 : 0.0;
+  const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
+                   (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+  while (n > 0) {
+    const int c = std::min(n, L.depth);
+    if (c >= 2) {
+      // a rank without neighbours reads its fixed ring only
+      if (mask != 0) {
+        Halo2D& h = *L.hk[L.cur][L.depth];
+        if (h.active()) {
+          h.start(s_);
+          h.finish(s_);
+        }
+      }
+      GMT_CHECK("mg fused smooth", gmt_mg_smooth_k(c, L.xo, L.nx, L.yo, L.ny, mask, L.up[L.cur], L.ld, L.sp, ldf, kC0,
+                                                   c1, o.omega, L.up[L.cur ^ 1], L.ld, s_));
+    } else {
+      mg_ring(l);
+      GMT_CHECK("mg smooth", gmt_mg_smooth(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, o.omega,
+                                           L.up[L.cur ^ 1], L.ld, s_));
+    }
+    L.cur ^= 1;
+    L.ring = false;
+    n -= c;
+  }
+}
+
 void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho) {
-  MgLevel& L = mg_[mgc_][l];
+  MgLevel& L = mg_[mgh_][l];
   const int64_t ldf = L.sp ? L.ld : 0;
   const double c1 = L.sp ? 1.0 : 0.0;
   if (l == levels - 1) {
@@ -1536,16 +1629,8 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
     }
     return;
   }
-  auto smooth = [&](int n) {
-    for (int i = 0; i < n; ++i) {
-      mg_ring(l);
-      GMT_CHECK("mg smooth", gmt_mg_smooth(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, o.omega,
-                                           L.up[L.cur ^ 1], L.ld, s_));
-      L.cur ^= 1;
-      L.ring = false;
-    }
-  };
-  MgLevel& C = mg_[mgc_][l + 1];
+  auto smooth = [&](int n) { mg_smooth_run(l, n, o); };
+  MgLevel& C = mg_[mgh_][l + 1];
   const int px = L.ox % 2 == 0 ? 1 : 0, py = L.oy % 2 == 0 ? 1 : 0;
   smooth(o.nu1);
   mg_ring(l);
@@ -1563,6 +1648,11 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
   else
     GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
                                              C.yo, C.ld, s_));
+  // a fused coarser level reads the ring of its source too
+  if (C.depth >= 2 && l + 1 < levels - 1 && C.hs[C.depth - 1] && C.hs[C.depth - 1]->active()) {
+    C.hs[C.depth - 1]->start(s_);
+    C.hs[C.depth - 1]->finish(s_);
+  }
   // u = 0 on the coarser level, ring included: current on every rank
   GMT_CHECK("memset", gmt_rt_memset_async(C.up[0], 0, C.u[0].bytes(), s_));
   C.cur = 0;
@@ -1588,9 +1678,10 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   const CheckLoop loop{"mg", "max_cycles", "jacobi mg check", o.tol, o.rtol, o.norm, o.max_cycles,
                        o.check_every == 0 ? 1 : o.check_every, o.lag, false};
   loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
-                    o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1),
+                    o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1) &&
+                    (o.fuse == 0 || (o.fuse >= 2 && o.fuse <= GMT_MG_MAX_FUSE)),
                 ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0, "
-                "coarsen 0 or 1");
+                "coarsen 0 or 1, fuse 0 or 2..4");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
   const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels, o.coarsen);
@@ -1602,6 +1693,7 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
              : o.coarsen == 0 ? "a rank of the process grid would own no coarse point"
                               : "the extents are too small or a rank of the process grid would own no coarse point"));
   mgc_ = o.coarsen;
+  mgh_ = o.coarsen + (o.fuse > 0 ? 2 : 0);
   mg_setup();
   const int levels = static_cast<int>(table.size());
   MgResult res;
@@ -1610,9 +1702,13 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   res.coarse_nx = table.back().second;
   res.coarse_rho = cheby_rho(res.coarse_nx, res.coarse_ny);
   res.coarse_iters = o.coarse_iters > 0 ? o.coarse_iters : mg_coarse_iters(res.coarse_rho);
-  MgLevel& F = mg_[mgc_][0];
+  MgLevel& F = mg_[mgh_][0];
   for (int b = 0; b < 2; ++b) F.up[b] = buf_[b].data();
   F.sp = src_f();
+  mg_fuse_setup(levels, o);
+  res.fuse = o.fuse;
+  res.fuse_fine = F.depth;
+  for (int l = 0; l + 1 < levels; ++l) res.fuse_levels += mg_[mgh_][l].depth >= 2;
   F.cur = parity_;
   F.ring = fresh_[parity_];
   run_checks(loop, res,

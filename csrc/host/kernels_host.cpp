@@ -465,6 +465,66 @@ int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* 
   return 0;
 }
 
+// k fused sweeps: the definition, on a copy of u's read set
+int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols) {
+  if (k < 1 || k > GMT_MG_MAX_FUSE) return 1;
+  const int64_t wc = k == 1 ? 128 : 128 - 2 * (k / 2 * 2);  // the gfx950 kernel's (csrc/kernels/mg.hip)
+  if (wave_cols) *wave_cols = wc;
+  if (block_cols) *block_cols = 4 * wc;
+  return 0;
+}
+
+int gmt_mg_smooth_k_path(int, int64_t, int64_t, int64_t, int, const double*, int64_t, const double*, int64_t,
+                         const double*, int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u, int64_t ld,
+                    const double* f, int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo,
+                    void*) {
+  if (k < 1 || k > GMT_MG_MAX_FUSE || halo_mask < 0 || halo_mask > 15) return 1;
+  if (nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
+             hn = halo_mask & GMT_MG_HALO_N;
+  const int64_t gw = hw ? k : 1, ge = he ? k : 1, gs = hs ? k : 1, gn = hn ? k : 1;
+  if (!u || !out || x0 < gw || y0 < gs || ld < x0 + nx + ge || ldo < x0 + nx || (f && ldf < x0 + nx + (ge - 1)))
+    return 1;
+  {  // u's read set against out[R], as address ranges
+    const double* ua = u + (y0 - gs) * ld + (x0 - gw);
+    const double* ub = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
+    const double* oa = out + y0 * ldo + x0;
+    const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
+    if (ua < oe && oa < ub) return 1;
+  }
+  // w: the read set, cell (0, 0) at (x0 - gw, y0 - gs); t: the level being computed
+  const int64_t wx = nx + gw + ge, wy = ny + gs + gn;
+  std::vector<double> w(static_cast<size_t>(wx * wy)), t;
+  for (int64_t y = 0; y < wy; ++y)
+    for (int64_t x = 0; x < wx; ++x) w[y * wx + x] = u[(y0 - gs + y) * ld + (x0 - gw + x)];
+  t = w;
+  for (int j = 1; j <= k; ++j) {
+    // B_j in w's coordinates
+    const int64_t bx0 = gw - (hw ? k - j : 0), bx1 = gw + nx + (he ? k - j : 0);
+    const int64_t by0 = gs - (hs ? k - j : 0), by1 = gs + ny + (hn ? k - j : 0);
+    for (int64_t y = by0; y < by1; ++y)
+      for (int64_t x = bx0; x < bx1; ++x) {
+        const double* c = w.data() + y * wx + x;
+        double o = c0 * ((c[-1] + c[1]) + (c[-wx] + c[wx]));
+        if (f) o = o + c1 * f[(y0 - gs + y) * ldf + (x0 - gw + x)];
+        const double d = o - c[0];
+        const double wt = omega * d;
+        t[y * wx + x] = c[0] + wt;
+      }
+    for (int64_t y = by0; y < by1; ++y)
+      for (int64_t x = bx0; x < bx1; ++x) w[y * wx + x] = t[y * wx + x];
+  }
+  for (int64_t y = 0; y < ny; ++y)
+    for (int64_t x = 0; x < nx; ++x) out[(y0 + y) * ldo + x0 + x] = w[(gs + y) * wx + gw + x];
+  return 0;
+}
+
 int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* d, int64_t ldd,
                     double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void*) {
   if (nx < 0 || ny < 0) return 1;

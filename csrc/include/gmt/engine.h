@@ -136,6 +136,7 @@ typedef struct gmt_engine_mg_opts {
   int max_levels;   /* 0 = no limit, else >= 2 */
   int coarse_iters; /* 0 = gmt_engine_mg_coarse_iters(rho of the coarsest level) */
   int coarsen;      /* 0 nested (nx + 1 and ny + 1 even on every level), 1 any lattice size (MgOpts::coarsen) */
+  int fuse;         /* 0, or 2..4: sweeps of a smoothing run per memory pass (MgOpts::fuse) */
 } gmt_engine_mg_opts;
 typedef struct gmt_engine_mg_result {
   int converged, iters, checks, residual_iters;
@@ -145,6 +146,7 @@ typedef struct gmt_engine_mg_result {
   int64_t coarse_ny, coarse_nx; /* global extents of the coarsest level */
   int coarse_iters;
   double coarse_rho;
+  int fuse, fuse_fine, fuse_levels; /* as requested; the depth of level 0; levels with a depth >= 2 */
 } gmt_engine_mg_result;
 /* 0; 1 on invalid options, 2 on an engine with a periodic axis, 3 when the
  * problem has no coarse level: nx + 1 or ny + 1 odd, 4 when a rank of the
@@ -159,6 +161,10 @@ int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels,
 /* the same under gmt_engine_mg_opts.coarsen (0: the table above); -1 on a bad argument */
 int gmt_engine_mg_levels2(int64_t ny, int64_t nx, int py, int px, int max_levels, int coarsen, int64_t* out,
                           int max);
+/* the depth of every smoothing level under gmt_engine_mg_opts.fuse on an engine of ghost depth `ghost`
+ * (gmt::mg_fuse_depths) into out[max]; returns their number, -1 on a bad argument */
+int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
+                              int coarsen, int* out, int max);
 /* 1 when the engine has a periodic axis */
 int gmt_engine_jacobi_periodic(void* h);
 /* out[16]: nx, ny, off_x, off_y, bytes_per_exchange, messages, graph, overlap, py, px, tsteps,

@@ -233,13 +233,35 @@ struct MgOpts {
   int max_levels = 0;            // 0: as many as the extents and the process grid allow; else >= 2
   int coarse_iters = 0;          // Chebyshev iterations on the coarsest level (0 = mg_coarse_iters(rho))
   int coarsen = 0;               // 0 nested; 1 any: every lattice size (both above)
+  int fuse = 0;                  // 0, or 2..GMT_MG_MAX_FUSE: sweeps of a smoothing run per memory pass (below)
 };
 struct MgResult : CheckResult {
   int levels = 0;                          // levels used, the fine one included
   int64_t coarse_ny = 0, coarse_nx = 0;    // global extents of the coarsest
   int coarse_iters = 0;                    // Chebyshev iterations on it
   double coarse_rho = 0.0;                 // and their spectral radius
+  int fuse = 0;                            // MgOpts::fuse as requested
+  int fuse_fine = 1;                       // the depth of level 0 (1: it smooths sweep by sweep)
+  int fuse_levels = 0;                     // smoothing levels with a depth >= 2
 };
+// MgOpts::fuse > 0 runs the sweeps of a smoothing run through gmt_mg_smooth_k,
+// up to `fuse` of them per memory pass, for the same bits.  Every smoothing
+// level l has a depth d_l, computed from global data only: the largest
+// d <= fuse such that, on each axis of the process grid with more than one
+// rank, every rank owns at least d cells of the level; on level 0 d <= the
+// engine's ghost depth too when the grid has more than one rank (an engine
+// with tsteps = 1 keeps its fine level unfused on several ranks, its coarse
+// levels fuse).  A run of n sweeps is chunks of min(n, d_l): a chunk of two or
+// more is one d_l-wide exchange of the current buffer with corners and one
+// gmt_mg_smooth_k whose halo sides are the sides with a neighbour; a chunk of
+// one is the single sweep above.  A level with neighbours keeps the
+// (d_l - 1)-wide ring of its source current: exchanged after each restriction
+// on coarse levels, once per source on level 0.  The coarse levels of such a
+// call have GMT_MG_MAX_FUSE ghost rows and columns (one hierarchy per coarsen
+// mode, built apart from the fuse = 0 ones, whose layout is unchanged).
+// The depth of each smoothing level (the coarsest level has none).
+std::vector<int> mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
+                                int coarsen);
 // The default coarse_iters: with sigma = (1 - sqrt(1 - rho^2))/rho and t = sigma,
 // the smallest k >= 1 with 2t/(1 + t^2) <= 0.1, t multiplied by sigma each
 // time k grows by one; 1 for rho = 0.
@@ -436,7 +458,9 @@ class JacobiSolver {
   // the ring of a field, `width` cells wide, with corners, or its faces only (collective)
   std::unique_ptr<Halo2D> ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny, int64_t ld,
                                     bool corners, int width = 1);
-  void mg_setup();          // the levels of mg() for mgc_ (first use; collective)
+  void mg_setup();          // the levels of mg() for mgh_ (first use; collective)
+  void mg_fuse_setup(int levels, const MgOpts& o);  // depths and the wide halo plans of a fused call (collective)
+  void mg_smooth_run(int l, int n, const MgOpts& o);  // n sweeps on level l, fused where its depth allows
   void mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho);
   void mg_ring(int l);      // the faces of level l's current buffer hold the neighbours' current values
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
@@ -488,7 +512,9 @@ class JacobiSolver {
   std::unique_ptr<Halo2D> cheby_halo_[2];
   // mg(): level 0 is buf_ and f_ with cheby_halo_ (u, s and the pair of halo
   // plans below stay empty there); coarser levels own their fields in buf_'s
-  // layout (interior origin x = 8, y = 1, pitch padded to 64, a zero ring)
+  // layout (interior origin x = 8, y = 1, pitch padded to 64, a zero ring);
+  // the hierarchies of fused calls (mg_[2], mg_[3]) give them
+  // GMT_MG_MAX_FUSE ghost rows and columns (y = 4, 4 columns right of the interior)
   struct MgLevel {
     int64_t ny_g = 0, nx_g = 0;                        // global interior
     int64_t nx = 0, ny = 0, ox = 0, oy = 0;            // this rank's share and its global offset
@@ -504,9 +530,18 @@ class JacobiSolver {
     int cur = 0;                                       // up[cur] is the level's current field
     bool ring = false;                                 // its faces are current
     std::unique_ptr<Halo2D> hu[2], hd;                 // rings with corners of u[0], u[1] and d
+    // fused smoothing (MgOpts::fuse): the smallest share of any rank on this
+    // level, the depth of the running call, and the w-wide rings with corners
+    // of either buffer and of the source, made on first use
+    int64_t min_nx = 0, min_ny = 0;
+    int depth = 1;
+    std::unique_ptr<Halo2D> hk[2][GMT_MG_MAX_FUSE + 1], hs[GMT_MG_MAX_FUSE];
+    double* hk_field[2] = {nullptr, nullptr};
   };
-  std::vector<MgLevel> mg_[2];  // by MgOpts::coarsen
-  int mgc_ = 0;                 // the hierarchy the running mg() uses
+  std::vector<MgLevel> mg_[4];  // by MgOpts::coarsen, + 2 for the layout of a fused call
+  int mgc_ = 0;                 // the coarsening of the running mg()
+  int mgh_ = 0;                 // the hierarchy it uses
+  int f_ring_ = 0;              // f_'s ring is current this wide (fused mg() on several ranks)
   Buffer<double> mg_ws_;  // gmt_cg_apply's workspace and its two results (level 0's size)
   Buffer<uint64_t> sig_;  // band-first completion signal (GMT_SPACE_FLAGS)
   bool fresh_[2] = {false, false};  // buf_[b]'s ghost ring holds the neighbours' current values

@@ -339,6 +339,46 @@ int gmt_mg_smooth_path(int64_t x0, int64_t nx, int64_t ny, const double* u, int6
 int gmt_mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc);
 int gmt_mg_prolong_add_path(int64_t x0, const double* e, int64_t lde, const double* u, int64_t ld);
 
+/* ---- k smoothing sweeps in one memory pass: out[R] = the k-th of k
+ *      applications of gmt_mg_smooth to u, R = nx x ny at (x0, y0), 16 B per
+ *      point (24 with f) whatever k.  halo_mask has one bit per side of R:
+ *      W = 1, E = 2, S = 4 (the lower row index), N = 8.
+ *        set bit   halo side: the k cells beyond R hold a neighbour's current
+ *                  cells; they are updatable
+ *        clear bit ring side: the one cell beyond R is fixed
+ *      B_j = R grown by k - j cells on each halo side (by 0 on a ring side);
+ *      U_0 = u; for j = 1..k: U_j = smooth(U_{j-1}) on B_j (gmt_mg_smooth's
+ *      cell, no contraction) and U_{j-1} everywhere else, so the ring cells
+ *      along a grown edge stay fixed; out[R] = U_k.  No other cell of out is
+ *      written (its ghost cells are stale afterwards).
+ *      u is read on R grown by k on halo sides and by 1 on ring sides, corners
+ *      included; f on R grown by k - 1 on halo sides and by 0 on ring sides;
+ *      nothing else is read.  Refused (non-zero, nothing launched, the same on
+ *      both backends): gmt_mg_smooth's refusals, k outside
+ *      1..GMT_MG_MAX_FUSE, a mask outside 0..15, x0 or y0 smaller than the
+ *      read set needs, a pitch shorter than the read set, u's read set
+ *      overlapping out[R].  An empty region launches nothing and returns 0;
+ *      k = 1 is gmt_mg_smooth.
+ *      The fast path (the alignment rule of gmt_mg_smooth) is a row walk that
+ *      carries k levels in registers, each level lagging the one below by a
+ *      row; a wave's valid columns shrink by one per level and side, so
+ *      neighbouring waves overlap by an even number of columns, and a row
+ *      segment runs k warm-up rows above and below its own. */
+#define GMT_MG_MAX_FUSE 4
+enum { GMT_MG_HALO_W = 1, GMT_MG_HALO_E = 2, GMT_MG_HALO_S = 4, GMT_MG_HALO_N = 8 };
+int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u, int64_t ld,
+                    const double* f, int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo,
+                    void* stream);
+/* GMT_PATH_ROW_WALK (*seg_rows, may be NULL, = the output rows per segment the
+ * launch would use) or GMT_PATH_SCALAR (one lane per output cell, each
+ * evaluating its own dependence cone; *seg_rows = 0); nothing launched.
+ * GMT_PATH_NONE on the CPU backend and for arguments the call would refuse. */
+int gmt_mg_smooth_k_path(int k, int64_t x0, int64_t nx, int64_t ny, int halo_mask, const double* u, int64_t ld,
+                         const double* f, int64_t ldf, const double* out, int64_t ldo, int64_t* seg_rows);
+/* Output columns per wave and per workgroup of the fast path for k sweeps
+ * (either pointer may be NULL); non-zero for k outside 1..GMT_MG_MAX_FUSE. */
+int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols);
+
 /* ---- Table-driven transfers between two levels that are not nested: n fine
  *      and m coarse interior points per axis on the same interval (any m with
  *      3 or 4 fine points between the neighbours of a coarse one), linear

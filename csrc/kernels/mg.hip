@@ -7,6 +7,9 @@
 //                       row_walk.hpp over u; the centre pair is the walk's own
 //                       row b, so a row adds one 16-B store and nothing else:
 //                       16 B/pt (24 with f).
+//   mg_smooth_k_walk    k of those sweeps in one pass (gmt_mg_smooth_k): the walk
+//                       with k levels in registers, described where it is
+//                       defined below; still 16 B/pt (24 with f).
 //   mg_restrict_pt      full weighting: one lane per pair of coarse cells, the
 //                       five fine columns of a row by two 16-B loads and one
 //                       8-B load, one 16-B store.  Neighbouring lanes and rows
@@ -122,6 +125,259 @@ static int mg_smooth_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64
     mg_smooth_scalar<HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, om, out, ldo);
   }
   GMT_RET_LAUNCH();
+}
+
+// ---- k fused sweeps of the smoother (gmt_mg_smooth_k, gmt/kernels.h) ----
+//
+//   mg_smooth_k_walk    the row walk with K levels in registers.  Level 0 is u;
+//                       level l + 1 lags level l by one row and keeps the two
+//                       last rows of level l as lane pairs (the third is the
+//                       row that just arrived), so one new row of u pushes one
+//                       row through every level and one row of level K to out.
+//                       W/E neighbours of every level come through DPP, so a
+//                       wave's valid columns shrink by one per level and side:
+//                       a wave stores kWalkWaveCols - 2*SH columns, SH = K - 1
+//                       rounded up to even (stores stay 16-B aligned), and
+//                       loads SH columns around them; a segment runs K rows
+//                       above and below its own.  Whether a cell is updated or
+//                       kept at a level (the boxes B_j) is a scalar test on
+//                       the row and a lane mask fixed for the walk: a select.
+//                       The outermost column of u's read set, where it is half
+//                       of a pair, comes by the walk's one-lane load, and is
+//                       that lane's W or E neighbour at every level: the cell
+//                       is never updated.
+//   mg_smooth_k_scalar  one lane per output cell: the cells of its dependence
+//                       cone (|dx| + |dy| <= K - j at level j) level by level
+//                       in registers, with the same cell and keep rule.
+
+constexpr int kMgMaxFuse = GMT_MG_MAX_FUSE;
+// the shortest segment: 4k rows rounded up to a power of two, so the 2k warm-up
+// rows stay at half the segment or below.  Small levels want short segments:
+// a wave walks its rows one after another, and with 32-row segments the
+// levels from 4095² down took longer fused than sweep by sweep.
+constexpr int64_t mg_fuse_min_seg(int k) { return k <= 2 ? 8 : 16; }
+
+constexpr int mg_fuse_shift(int k) { return k / 2 * 2; }  // k - 1 rounded up to even
+constexpr int mg_fuse_wave_cols(int k) { return k == 1 ? kWalkWaveCols : kWalkWaveCols - 2 * mg_fuse_shift(k); }
+
+struct MgFuseArgs {
+  int64_t x0, nx, y0, ny;
+  int mask;
+  const double* u;
+  int64_t ld;
+  const double* f;
+  int64_t ldf;
+  double c0, c1, om;
+  double* out;
+  int64_t ldo;
+  int64_t nseg, seg_rows, nblocks;
+};
+
+__device__ __forceinline__ int64_t mg_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+template <int K, bool HAS_F>
+__global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
+  constexpr int SH = mg_fuse_shift(K), OC = mg_fuse_wave_cols(K);
+  constexpr int U = HAS_F ? kMgUnrollF : kMgUnrollP;
+  const double* __restrict__ u = a.u;
+  const double* __restrict__ f = a.f;
+  double* __restrict__ out = a.out;
+  const int64_t nx = a.nx, ny = a.ny, ld = a.ld, ldf = a.ldf;
+  const int64_t t = xcd_swizzle(blockIdx.x, a.nblocks);
+  const int64_t seg = t % a.nseg, bx = t / a.nseg;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int64_t xo = (bx * (kBlock / kWave) + wave) * OC;  // the wave's first output column
+  if (xo >= nx) return;  // wave-uniform: every lane of a working wave stays active (DPP)
+  const int64_t xe = xo + OC < nx ? xo + OC : nx;
+  const bool hw = a.mask & GMT_MG_HALO_W, he = a.mask & GMT_MG_HALO_E, hs = a.mask & GMT_MG_HALO_S,
+             hn = a.mask & GMT_MG_HALO_N;
+  // region-relative columns: the lane's own pair, u's read set [lo, hi), its first and last whole pair
+  const int64_t c = xo - SH + 2 * lane;
+  const int64_t lo = hw ? -K : -1, hi = nx + (he ? K : 1);
+  const int64_t lop = lo + (lo & 1), hip = (hi - 2) & ~int64_t(1);
+  const int64_t cl = mg_clamp(c, lop, hip);  // lanes outside re-read a pair inside (never used)
+  const bool west = lane == 0 || c == lop, east = lane == kWave - 1 || c == hip;
+  const bool wld = west && c - 1 >= lo && c - 1 < hi, eld = east && c + 2 >= lo && c + 2 < hi;
+  // updated at level l + 1 or kept: the column masks of the lane's two cells
+  bool mx[K], my[K];
+#pragma unroll
+  for (int l = 0; l < K; ++l) {
+    const int64_t bl = hw ? -(K - 1 - l) : 0, bh = nx + (he ? K - 1 - l : 0);
+    mx[l] = c >= bl && c < bh;
+    my[l] = c + 1 >= bl && c + 1 < bh;
+  }
+  // f's read set: a lane loads a whole pair, one cell of it, or nothing
+  const int64_t flo = hw ? -(K - 1) : 0, fhi = nx + (he ? K - 1 : 0);
+  const bool fxo = HAS_F && c >= flo && c < fhi, fyo = HAS_F && c + 1 >= flo && c + 1 < fhi;
+  const bool sp = c >= xo && c + 1 < xe, s1 = c >= xo && c < xe && !sp;
+  const int64_t r0 = seg * a.seg_rows;
+  const int64_t r1 = r0 + a.seg_rows < ny ? r0 + a.seg_rows : ny;
+  const int64_t rlo = hs ? -K : -1, rhi = ny - 1 + (hn ? K : 1);             // u's rows
+  const int64_t frlo = hs ? -(K - 1) : 0, frhi = ny - 1 + (hn ? K - 1 : 0);  // f's rows
+  const double* ub = u + a.y0 * ld + a.x0;
+  const double* fb = HAS_F ? f + a.y0 * ldf + a.x0 : nullptr;
+  double* ob = out + a.y0 * a.ldo + a.x0 + c;
+  d2 A[K], B[K], fh[K];
+  double wh[K], eh[K];
+#pragma unroll
+  for (int l = 0; l < K; ++l) {
+    A[l] = B[l] = fh[l] = d2{0.0, 0.0};
+    wh[l] = eh[l] = 0.0;
+  }
+  for (int64_t tt = r0 - K; tt < r1 + K; tt += U) {
+    d2 cn[U], fn[U];
+    double wn[U], en[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      // rows past the read set are clamped to its last ones (loaded, not used)
+      const double* p = ub + mg_clamp(tt + j, rlo, rhi) * ld;
+      cn[j] = ld2(p + cl);
+      wn[j] = en[j] = 0.0;
+      if (wld) wn[j] = p[c - 1];
+      if (eld) en[j] = p[c + 2];
+      fn[j] = d2{0.0, 0.0};
+      if (HAS_F) {  // the row level 1 computes when row tt + j arrives
+        const double* pf = fb + mg_clamp(tt + j - 1, frlo, frhi) * ldf;
+        if (fxo && fyo) {
+          fn[j] = ld2(pf + c);
+        } else {
+          if (fxo) fn[j].x = pf[c];
+          if (fyo) fn[j].y = pf[c + 1];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int64_t tr = tt + j;  // the row of u that arrives; level l + 1 computes row tr - 1 - l
+      if (HAS_F) {
+#pragma unroll
+        for (int l = K - 1; l > 0; --l) fh[l] = fh[l - 1];
+        fh[0] = fn[j];
+      }
+      d2 C = cn[j];
+#pragma unroll
+      for (int l = 0; l < K; ++l) {
+        const int64_t y = tr - 1 - l;
+        const bool rok = y >= (hs ? -(K - 1 - l) : 0) && y < ny + (hn ? K - 1 - l : 0);
+        const d2 b = B[l];
+        const double wl = dpp_from_lower(b.y), eu = dpp_from_upper(b.x);
+        const double w = west ? wh[l] : wl, e = east ? eh[l] : eu;
+        d2 n;
+        n.x = mg_smooth_cell<HAS_F>(w, b.y, A[l].x, C.x, b.x, a.c0, a.c1, fh[l].x, a.om);
+        n.y = mg_smooth_cell<HAS_F>(b.x, e, A[l].y, C.y, b.y, a.c0, a.c1, fh[l].y, a.om);
+        n.x = rok && mx[l] ? n.x : b.x;
+        n.y = rok && my[l] ? n.y : b.y;
+        A[l] = b;
+        B[l] = C;
+        C = n;
+      }
+#pragma unroll
+      for (int l = K - 1; l > 0; --l) wh[l] = wh[l - 1], eh[l] = eh[l - 1];
+      wh[0] = wn[j], eh[0] = en[j];
+      const int64_t yo = tr - K;  // the row of level K that came out
+      if (yo >= r0 && yo < r1) {
+        if (sp)
+          st2(ob + yo * a.ldo, C);
+        else if (s1)
+          ob[yo * a.ldo] = C.x;
+      }
+    }
+  }
+}
+
+template <int K, bool HAS_F>
+__global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgFuseArgs a) {
+  const double* __restrict__ u = a.u;
+  const double* __restrict__ f = a.f;
+  const int64_t nx = a.nx, ny = a.ny;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= nx * ny) return;
+  const int64_t x = i % nx, y = i / nx;  // region-relative
+  const bool hw = a.mask & GMT_MG_HALO_W, he = a.mask & GMT_MG_HALO_E, hs = a.mask & GMT_MG_HALO_S,
+             hn = a.mask & GMT_MG_HALO_N;
+  const double* ub = u + a.y0 * a.ld + a.x0;
+  const double* fb = HAS_F ? f + a.y0 * a.ldf + a.x0 : nullptr;
+  double v[2 * K + 1][2 * K + 1], n[2 * K + 1][2 * K + 1];  // indices are constants once unrolled: registers
+  const int64_t lo = hw ? -K : -1, hi = nx + (he ? K : 1), rlo = hs ? -K : -1, rhi = ny + (hn ? K : 1);
+#pragma unroll
+  for (int dy = -K; dy <= K; ++dy)
+#pragma unroll
+    for (int dx = -K; dx <= K; ++dx)
+      if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) <= K) {
+        const int64_t X = x + dx, Y = y + dy;
+        const bool in = X >= lo && X < hi && Y >= rlo && Y < rhi;
+        v[dy + K][dx + K] = in ? ub[Y * a.ld + X] : 0.0;
+      }
+#pragma unroll
+  for (int j = 1; j <= K; ++j) {
+    const int64_t bxl = hw ? -(K - j) : 0, bxh = nx + (he ? K - j : 0);
+    const int64_t byl = hs ? -(K - j) : 0, byh = ny + (hn ? K - j : 0);
+#pragma unroll
+    for (int dy = -K; dy <= K; ++dy)
+#pragma unroll
+      for (int dx = -K; dx <= K; ++dx)
+        if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) <= K - j) {
+          const int64_t X = x + dx, Y = y + dy;
+          const double cv = v[dy + K][dx + K];
+          double r = cv;
+          if (X >= bxl && X < bxh && Y >= byl && Y < byh)
+            r = mg_smooth_cell<HAS_F>(v[dy + K][dx + K - 1], v[dy + K][dx + K + 1], v[dy + K - 1][dx + K],
+                                      v[dy + K + 1][dx + K], cv, a.c0, a.c1, HAS_F ? fb[Y * a.ldf + X] : 0.0, a.om);
+          n[dy + K][dx + K] = r;
+        }
+#pragma unroll
+    for (int dy = -K; dy <= K; ++dy)
+#pragma unroll
+      for (int dx = -K; dx <= K; ++dx)
+        if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) <= K - j) v[dy + K][dx + K] = n[dy + K][dx + K];
+  }
+  a.out[(a.y0 + y) * a.ldo + a.x0 + x] = v[K][K];
+}
+
+// rows per segment of the fused walk: the row walk's rule with its own floor
+static int64_t mg_fuse_seg_rows(int k, int64_t nx, int64_t ny) {
+  const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(k)) * (kBlock / kWave);
+  const int64_t nbx = (nx + bc - 1) / bc;
+  int64_t L = kWalkMaxSeg;
+  while (L > mg_fuse_min_seg(k) && nbx * ((ny + L - 1) / L) < 8 * static_cast<int64_t>(walk_cus())) L /= 2;
+  return L;
+}
+
+// gmt_mg_smooth_k takes these arguments (a non-empty region, k and the mask in range)
+static bool mg_fuse_args_ok(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int mask, const double* u,
+                            int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo) {
+  const int64_t gw = mask & GMT_MG_HALO_W ? k : 1, ge = mask & GMT_MG_HALO_E ? k : 1;
+  const int64_t gs = mask & GMT_MG_HALO_S ? k : 1, gn = mask & GMT_MG_HALO_N ? k : 1;
+  if (!u || !out || x0 < gw || y0 < gs || ld < x0 + nx + ge || ldo < x0 + nx || (f && ldf < x0 + nx + (ge - 1)))
+    return false;
+  // u's read set against out[R], as address ranges
+  const double* ua = u + (y0 - gs) * ld + (x0 - gw);
+  const double* ub = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
+  const double* oa = out + y0 * ldo + x0;
+  const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
+  return !(ua < oe && oa < ub);
+}
+
+template <int K, bool HAS_F>
+static int mg_smooth_k_launch(bool walk, MgFuseArgs a, hipStream_t s) {
+  if (walk) {
+    const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(K)) * (kBlock / kWave);
+    a.seg_rows = mg_fuse_seg_rows(K, a.nx, a.ny);
+    a.nseg = (a.ny + a.seg_rows - 1) / a.seg_rows;
+    a.nblocks = (a.nx + bc - 1) / bc * a.nseg;
+    if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
+    mg_smooth_k_walk<K, HAS_F><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
+  } else {
+    const int64_t nb = (a.nx * a.ny + kBlock - 1) / kBlock;
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    mg_smooth_k_scalar<K, HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(a);
+  }
+  GMT_RET_LAUNCH();
+}
+
+template <int K>
+static int mg_smooth_k_launch_f(bool walk, const MgFuseArgs& a, hipStream_t s) {
+  return a.f ? mg_smooth_k_launch<K, true>(walk, a, s) : mg_smooth_k_launch<K, false>(walk, a, s);
 }
 
 // ---- full weighting ----
@@ -426,6 +682,46 @@ extern "C" int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, con
   const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
   return f ? mg_smooth_launch<true>(walk, x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, s)
            : mg_smooth_launch<false>(walk, x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, s);
+}
+
+extern "C" int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols) {
+  using namespace gmt;
+  if (k < 1 || k > kMgMaxFuse) return static_cast<int>(hipErrorInvalidValue);
+  if (wave_cols) *wave_cols = mg_fuse_wave_cols(k);
+  if (block_cols) *block_cols = static_cast<int64_t>(mg_fuse_wave_cols(k)) * (kBlock / kWave);
+  return 0;
+}
+
+extern "C" int gmt_mg_smooth_k_path(int k, int64_t x0, int64_t nx, int64_t ny, int halo_mask, const double* u,
+                                    int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo,
+                                    int64_t* seg_rows) {
+  using namespace gmt;
+  if (seg_rows) *seg_rows = 0;
+  if (k < 1 || k > kMgMaxFuse || halo_mask < 0 || halo_mask > 15) return GMT_PATH_NONE;
+  if (k == 1) return gmt_mg_smooth_path(x0, nx, ny, u, ld, f, ldf, out, ldo, seg_rows);
+  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);
+  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(k, nx, ny);
+  return path;
+}
+
+extern "C" int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u,
+                               int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega,
+                               double* out, int64_t ldo, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (k < 1 || k > kMgMaxFuse || halo_mask < 0 || halo_mask > 15) return static_cast<int>(hipErrorInvalidValue);
+  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
+  if (nx == 0 || ny == 0) return 0;
+  if (!mg_fuse_args_ok(k, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo))
+    return static_cast<int>(hipErrorInvalidValue);
+  if (k == 1) return gmt_mg_smooth(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, stream);
+  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
+  const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0};
+  switch (k) {
+    case 2: return mg_smooth_k_launch_f<2>(walk, a, s);
+    case 3: return mg_smooth_k_launch_f<3>(walk, a, s);
+    default: return mg_smooth_k_launch_f<4>(walk, a, s);
+  }
 }
 
 extern "C" int gmt_mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc,

@@ -106,7 +106,7 @@ __device__ __forceinline__ void write_block_partials(double acc, double m, doubl
 // Rows per segment: as long as possible (two extra row loads per segment)
 // while the launch still has 8 workgroups per compute unit, the most a CU
 // holds.  A function of the region and the device only.
-inline int64_t walk_seg_rows(int64_t nx, int64_t ny) {
+inline int walk_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -114,6 +114,10 @@ inline int64_t walk_seg_rows(int64_t nx, int64_t ny) {
       n = 256;
     return n;
   }();
+  return cus;
+}
+inline int64_t walk_seg_rows(int64_t nx, int64_t ny) {
+  const int cus = walk_cus();
   const int64_t nbx = (nx + kWalkBlockCols - 1) / kWalkBlockCols;
   int64_t L = kWalkMaxSeg;
   while (L > kWalkMinSeg && nbx * ((ny + L - 1) / L) < 8 * static_cast<int64_t>(cus)) L /= 2;

@@ -178,6 +178,13 @@ _SIGS = {
         [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
     ),
     "gmt_mg_smooth_path": (c_int, [c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_mg_smooth_k": (
+        c_int,
+        [c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
+    ),
+    "gmt_mg_smooth_k_path": (
+        c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gmt_mg_smooth_k_geom": (c_int, [c_int, c_vp, c_vp]),
     "gmt_mg_restrict": (
         c_int,
         [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_dbl, c_vp, c_i64, c_i64, c_i64, c_vp],

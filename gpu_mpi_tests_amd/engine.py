@@ -103,7 +103,8 @@ class MgOpts(ctypes.Structure):
     _fields_ = [("tol", ctypes.c_double), ("rtol", ctypes.c_double), ("norm", ctypes.c_int),
                 ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
                 ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
-                ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int)]
+                ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int),
+                ("fuse", ctypes.c_int)]
 
 
 class MgResult(ctypes.Structure):
@@ -112,11 +113,13 @@ class MgResult(ctypes.Structure):
                 ("residual_iters", ctypes.c_int), ("residual", ctypes.c_double),
                 ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("failed", ctypes.c_int),
                 ("levels", ctypes.c_int), ("coarse_ny", ctypes.c_int64), ("coarse_nx", ctypes.c_int64),
-                ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double)]
+                ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double),
+                ("fuse", ctypes.c_int), ("fuse_fine", ctypes.c_int), ("fuse_levels", ctypes.c_int)]
 
 
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
 COARSEN = {"nested": 0, "any": 1}  # MgOpts::coarsen
+MG_MAX_FUSE = 4  # GMT_MG_MAX_FUSE: the largest MgOpts::fuse
 CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
 
@@ -690,7 +693,7 @@ class NativeJacobi:
 
     def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
            lag: int = 1, nu: tuple = (2, 2), omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0,
-           coarsen: str = "nested") -> dict:
+           coarsen: str = "nested", fuse: int = 0) -> dict:
         """Geometric multigrid V-cycles from the current field
         (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
         ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
@@ -711,7 +714,15 @@ class NativeJacobi:
         the same on every process grid.  Returns the fields of MgResult:
         ``converged``, ``iters`` (cycles), ``checks``, ``residual_iters``,
         ``residual``, ``residual_max``, ``r0``, ``failed``, ``levels``,
-        ``coarse_ny``, ``coarse_nx``, ``coarse_iters``, ``coarse_rho``.
+        ``coarse_ny``, ``coarse_nx``, ``coarse_iters``, ``coarse_rho``,
+        ``fuse``, ``fuse_fine``, ``fuse_levels``.
+        ``fuse`` (0, or 2..4) runs up to that many sweeps of a smoothing run in
+        one memory pass (gmt_mg_smooth_k) behind one exchange as wide, for the
+        same bits: every level has the depth :func:`mg_fuse_depths` gives it (a
+        rank needs that many cells of the level on every axis it shares, and
+        level 0 the engine's ghost depth: ``tsteps=1`` keeps the fine level of
+        a multi-rank engine unfused while its coarse levels fuse); ``fuse_fine``
+        is level 0's depth, ``fuse_levels`` the levels of depth >= 2.
         Identical on every rank.  ValueError on bad options, a periodic axis,
         or a problem with no coarse level (``nx + 1`` or ``ny + 1`` odd, or a
         rank that would own no coarse point).  Collective."""
@@ -736,9 +747,11 @@ class NativeJacobi:
             raise ValueError("max_levels must be 0 or >= 2 and coarse_iters >= 0")
         if coarsen not in COARSEN:
             raise ValueError(f"coarsen must be one of {sorted(COARSEN)}, got {coarsen!r}")
+        if isinstance(fuse, bool) or int(fuse) != fuse or not (int(fuse) == 0 or 2 <= int(fuse) <= MG_MAX_FUSE):
+            raise ValueError(f"fuse must be 0 or 2..{MG_MAX_FUSE}, got {fuse!r}")
         o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
                    nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters),
-                   coarsen=COARSEN[coarsen])
+                   coarsen=COARSEN[coarsen], fuse=int(fuse))
         r = MgResult()
         rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
         if rc == 2:
@@ -1103,7 +1116,8 @@ def mg_axis_table(n: int, m: int):
     return mg_tab.axis_table(n, m)
 
 
-def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0, coarsen: str = "nested") -> list:
+def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0, coarsen: str = "nested",
+              _shares: "list | None" = None) -> list:
     """The level table of :meth:`NativeJacobi.mg`: global ``(ny, nx)`` of every
     level, the fine one first.  ``coarsen="nested"``: a level has the coarser
     level ``((ny-1)/2, (nx-1)/2)`` while ``nx + 1`` and ``ny + 1`` are even,
@@ -1140,6 +1154,8 @@ def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0, coars
 
     by, bx = bounds(ny, int(dims[0])), bounds(nx, int(dims[1]))
     out = [(ny, nx)]
+    if _shares is not None:
+        _shares.append((by, bx))
     while max_levels == 0 or len(out) < max_levels:
         if coarsen == "nested":
             if ny % 2 == 0 or nx % 2 == 0:
@@ -1158,6 +1174,31 @@ def mg_levels(ny: int, nx: int, dims: tuple = (1, 1), max_levels: int = 0, coars
                 break
             (ny, by), (nx, bx) = (my, cy), (mx, cx)
         out.append((ny, nx))
+        if _shares is not None:
+            _shares.append((by, bx))
+    return out
+
+
+def mg_fuse_depths(ny: int, nx: int, dims: tuple, fuse: int, ghost: int, max_levels: int = 0,
+                   coarsen: str = "nested") -> list:
+    """The depth of every smoothing level of ``mg(fuse=...)`` (the coarsest
+    level has none), level 0 first: the largest ``d <= fuse`` such that on each
+    axis of the ``dims = (py, px)`` grid with more than one rank every rank
+    owns at least ``d`` cells of the level (the shares of :func:`mg_levels`),
+    and on level 0 ``d <= ghost`` (the engine's ghost depth, its ``tsteps``)
+    when the grid has more than one rank.  1: the level smooths sweep by sweep.
+    The Python model of gmt::mg_fuse_depths."""
+    shares = []
+    levels = mg_levels(ny, nx, dims, max_levels, coarsen, shares)
+    out = []
+    for l, (by, bx) in enumerate(shares[:len(levels) - 1]):
+        d = max(int(fuse), 1)
+        for b in (by, bx):
+            if len(b) > 2:
+                d = min(d, min(b1 - b0 for b0, b1 in zip(b, b[1:])))
+        if l == 0 and int(dims[0]) * int(dims[1]) > 1:
+            d = min(d, int(ghost))
+        out.append(max(d, 1))
     return out
 
 

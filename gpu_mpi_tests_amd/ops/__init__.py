@@ -8,7 +8,8 @@ and the BASELINE 5-point Jacobi ``jacobi5`` / ``jacobi5_rects`` (single sweep),
 its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
 ``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``,
 the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
-``mg_prolong_add``, their table-driven forms for levels that are not nested
+``mg_prolong_add``, the fused smoother ``mg_smooth_k`` (k sweeps per memory
+pass), the table-driven transfers for levels that are not nested
 ``mg_restrict_tab`` / ``mg_prolong_add_tab``, and ``jacobi5tb`` (K fused sweeps
 per memory pass).
 """
@@ -51,6 +52,9 @@ from .kernels import (  # noqa: F401
     mg_restrict_tab,
     mg_restrict_tab_path,
     mg_smooth,
+    mg_smooth_k,
+    mg_smooth_k_geom,
+    mg_smooth_k_path,
     mg_smooth_path,
     jacobi5xk,
     jacobi5tb,

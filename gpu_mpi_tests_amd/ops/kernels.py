@@ -613,6 +613,51 @@ def mg_smooth_path(u: torch.Tensor, out: torch.Tensor, region: tuple[int, int, i
     return int(path), int(seg.value)
 
 
+def mg_smooth_k(u: torch.Tensor, out: torch.Tensor, omega: float, region: tuple[int, int, int, int], k: int,
+                halo_mask: int = 0, f: torch.Tensor | None = None, c0: float = 0.25, c1: float = 1.0) -> torch.Tensor:
+    """``k`` (1..4) sweeps of :func:`mg_smooth` over ``region`` in one memory
+    pass (gmt_mg_smooth_k).  ``halo_mask`` (W = 1, E = 2, S = 4, N = 8): a set
+    bit marks a side whose ``k`` cells beyond the region are a neighbour's
+    current cells and are updated along (on a box that shrinks by one cell per
+    sweep); a clear bit a side whose one cell beyond the region is fixed.
+    Bitwise :func:`reference.mg_smooth_k`.  ``u`` and ``out`` must not share
+    storage.  Returns ``out``."""
+    _check2d(u, "mg_smooth_k.u")
+    _check2d(out, "mg_smooth_k.out")
+    if f is not None:
+        _check2d(f, "mg_smooth_k.f")
+    if _overlap(u, out):
+        raise ValueError("mg_smooth_k: u and out must not share storage")
+    x0, nx, y0, ny = (int(t) for t in region)
+    if not _is_dev(out):
+        return ref.mg_smooth_k(u, out, omega, x0, nx, y0, ny, int(k), int(halo_mask), f, c0, c1)
+    _native.check(_native.lib().gmt_mg_smooth_k(int(k), x0, nx, y0, ny, int(halo_mask), u.data_ptr(), u.stride(0),
+                                                *_ptr_ld(f), float(c0), float(c1), float(omega), out.data_ptr(),
+                                                out.stride(0), _stream(out)), "gmt_mg_smooth_k")
+    return out
+
+
+def mg_smooth_k_path(u: torch.Tensor, out: torch.Tensor, region: tuple[int, int, int, int], k: int,
+                     halo_mask: int = 0, f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`mg_smooth_k` would launch (gmt_mg_smooth_k_path, no
+    launch): ``(PATH_ROW_WALK or PATH_SCALAR, output rows per segment of the fused walk)``."""
+    x0, nx, _, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_mg_smooth_k_path(int(k), x0, nx, ny, int(halo_mask), u.data_ptr(), u.stride(0),
+                                              *_ptr_ld(f), out.data_ptr(), out.stride(0),
+                                              ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def mg_smooth_k_geom(k: int) -> tuple[int, int]:
+    """``(output columns per wave, per workgroup)`` of the fused walk for ``k`` sweeps (gmt_mg_smooth_k_geom)."""
+    wc, bc = ctypes.c_int64(0), ctypes.c_int64(0)
+    if _native.lib().gmt_mg_smooth_k_geom(int(k), ctypes.cast(ctypes.pointer(wc), ctypes.c_void_p),
+                                          ctypes.cast(ctypes.pointer(bc), ctypes.c_void_p)) != 0:
+        raise ValueError(f"mg_smooth_k_geom: k = {k} outside 1..4")
+    return int(wc.value), int(bc.value)
+
+
 def mg_restrict(d: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
                 coarse: tuple[int, int], cs: float = 0.25) -> torch.Tensor:
     """Full weighting of the fine field ``d`` over ``region = (x0, nx, y0, ny)``

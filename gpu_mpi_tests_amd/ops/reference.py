@@ -190,6 +190,36 @@ def mg_smooth(u, out, omega: float, x0: int, nx: int, y0: int, ny: int, f=None, 
     return out
 
 
+MG_MAX_FUSE = 4
+MG_HALO_W, MG_HALO_E, MG_HALO_S, MG_HALO_N = 1, 2, 4, 8
+
+
+def mg_smooth_k(u, out, omega: float, x0: int, nx: int, y0: int, ny: int, k: int, halo_mask: int = 0, f=None,
+                c0: float = 0.25, c1: float = 1.0):
+    """gmt_mg_smooth_k: ``k`` applications of :func:`mg_smooth` over a copy of
+    ``u``, the j-th on the region grown by ``k - j`` cells on every side whose
+    bit is set in ``halo_mask`` (W = 1, E = 2, S = 4, N = 8) and by none on the
+    others; every cell outside a box keeps its value.  ``out[region]`` gets the
+    last one; no other cell of ``out`` is written.  Works on torch tensors and
+    NumPy arrays alike."""
+    if not 1 <= k <= MG_MAX_FUSE or not 0 <= halo_mask <= 15:
+        raise ValueError("mg_smooth_k: k outside 1..4 or a mask outside 0..15")
+    if nx < 0 or ny < 0:
+        raise ValueError("mg_smooth_k: negative extent")
+    if nx > 0 and ny > 0:
+        a = u.clone() if hasattr(u, "clone") else u.copy()
+        b = u.clone() if hasattr(u, "clone") else u.copy()
+        for j in range(1, k + 1):
+            g = k - j
+            gw, ge = (g if halo_mask & MG_HALO_W else 0), (g if halo_mask & MG_HALO_E else 0)
+            gs, gn = (g if halo_mask & MG_HALO_S else 0), (g if halo_mask & MG_HALO_N else 0)
+            bx, by, bnx, bny = x0 - gw, y0 - gs, nx + gw + ge, ny + gs + gn
+            mg_smooth(a, b, omega, bx, bnx, by, bny, f, c0, c1)
+            a[by : by + bny, bx : bx + bnx] = b[by : by + bny, bx : bx + bnx]
+        out[y0 : y0 + ny, x0 : x0 + nx] = a[y0 : y0 + ny, x0 : x0 + nx]
+    return out
+
+
 def mg_coarse_extent(n: int, p: int) -> int:
     """Coarse cells of a fine region of n cells whose first coarse point has the region-relative index p."""
     return (n - p + 1) // 2
