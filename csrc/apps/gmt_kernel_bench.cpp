@@ -25,7 +25,10 @@
 //      gmt_mg_prolong_add 18) on N x N (default 8191; an even N times them at
 //      N - 1 and the table-driven transfers of coarsen = any at N), as --only=cg;
 //      then the fused smoother gmt_mg_smooth_k for k = 2, 3, 4 without and with
-//      f, compared bitwise with k single sweeps and timed beside them and DAXPY
+//      f, compared bitwise with k single sweeps and timed beside them and DAXPY,
+//      and the red-black smoother gmt_mg_smooth_rb for h = 1, 2, 4 half-sweeps
+//      without and with f, compared bitwise with h launches of h = 1 and timed
+//      beside gmt_mg_smooth_k of k = h
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -632,6 +635,63 @@ int main(int argc, char** argv) {
           std::printf("mg %lldx%lld  %s ms / %d x mg_smooth ms = %.4f, GB/s / daxpy GB/s = %.4f  (best of %d)\n",
                       (long long)n, (long long)n, nm, k, st[0].min() / st[1].min(),
                       (bpp / st[0].min()) / (24.0 / st[2].min()), reps);
+        }
+    }
+    {
+      // the red-black smoother (gmt_mg_smooth_rb, mask 0, par 0) for h = 1, 2, 4 half-sweeps without and with
+      // f: first compared bitwise with h launches of h = 1 whose par alternates, between two buffers that hold
+      // u's ring, then timed beside gmt_mg_smooth_k of k = h (the same walk without the colour) in the order
+      // A B B A.  GB/s from the same compulsory 16 (24) bytes a point.
+      Buffer<double> w(elems, GMT_SPACE_DEVICE), x(elems, GMT_SPACE_DEVICE);
+      Buffer<double> dws(static_cast<size_t>(2 * gmt_diff_sq_workspace(n, n)) + 2, GMT_SPACE_DEVICE);
+      GMT_CHECK("memset", gmt_rt_memset_async(w.data(), 0, w.bytes(), s));
+      for (int h : {1, 2, 4})
+        for (int wf = 0; wf < 2; ++wf) {
+          for (double* b : {u.data(), v.data(), x.data()})
+            GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, b, ld, s));
+          const double* fp = wf ? f.data() : nullptr;
+          const int64_t ldf = wf ? ld : 0;
+          const double c1 = wf ? 1.0 : 0.0, bpp = wf ? 24.0 : 16.0;
+          char nm[32], nmk[32];
+          std::snprintf(nm, sizeof(nm), "mg_smooth_rb%d%s", h, wf ? "_f" : "");
+          std::snprintf(nmk, sizeof(nmk), "mg_smooth_k%d%s", h, wf ? "_f" : "");
+          const std::function<void()> rb = [&] {
+            GMT_CHECK(nm, gmt_mg_smooth_rb(h, 0, xo, n, 1, n, 0, u.data(), ld, fp, ldf, 0.25, c1, 1.0, w.data(), ld, s));
+          };
+          const std::function<void()> jac = [&] {
+            GMT_CHECK(nmk, gmt_mg_smooth_k(h, xo, n, 1, n, 0, u.data(), ld, fp, ldf, 0.25, c1, 0.8, w.data(), ld, s));
+          };
+          int64_t segh = 0;
+          const int ph = gmt_mg_smooth_rb_path(h, 0, xo, n, n, 0, u.data(), ld, fp, ldf, w.data(), ld, &segh);
+          rb();
+          const double* src = u.data();  // u -> v -> x -> v ...
+          for (int j = 0; j < h; ++j) {
+            double* dst = j % 2 == 0 ? v.data() : x.data();
+            GMT_CHECK(nm, gmt_mg_smooth_rb(1, j % 2, xo, n, 1, n, 0, src, ld, fp, ldf, 0.25, c1, 1.0, dst, ld, s));
+            src = dst;
+          }
+          GMT_CHECK("diff", gmt_diff_bits(n, n, w.data() + ld + xo, ld, src + ld + xo, ld, dws.data(), dws.data() + 2, s));
+          double dres[2] = {-1.0, -1.0};
+          GMT_CHECK("D2H", gmt_rt_memcpy_async(dres, dws.data(), sizeof(dres), s));
+          GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+          std::printf("mg %lldx%lld  %s path %d (%lld rows per segment), %s bitwise %d x mg_smooth_rb1: %s\n",
+                      (long long)n, (long long)n, nm, ph, (long long)segh, nm, h, dres[1] == 0.0 ? "yes" : "NO");
+          if (dres[1] != 0.0) return 1;
+          Stats st[2];
+          const int order[4] = {0, 1, 1, 0};
+          for (int rep = 0; rep < reps; ++rep)
+            for (int o = 0; o < 4; ++o) {
+              const double ms = time_ms(s, iters, order[o] == 0 ? rb : jac);
+              st[order[o]].add(ms);
+              std::printf("mg %lldx%lld rep %d  %-18s %9.4f ms\n", (long long)n, (long long)n, rep,
+                          order[o] == 0 ? nm : nmk, ms);
+            }
+          char shape[64];
+          std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+          report(nm, 0, shape, st[0].min(), bpp * n * n);
+          report(nmk, 0, shape, st[1].min(), bpp * n * n);
+          std::printf("mg %lldx%lld  %s ms / %s ms = %.4f  (best of %d)\n", (long long)n, (long long)n, nm, nmk,
+                      st[0].min() / st[1].min(), reps);
         }
     }
     if (nt % 2 == 0) {

@@ -59,6 +59,7 @@
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
 //   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any] [--fuse=K]
+//        [--smoother=jacobi|rb]
 //                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
 //                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
 //                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
@@ -68,7 +69,9 @@
 //                           (default: from its spectral radius).  --check runs the same number of
 //                           serial cycles and compares within 1e-10 * max|u0|.  K (0, or 2..4) runs
 //                           up to K sweeps of a smoothing run in one memory pass (MgOpts::fuse) for
-//                           the same bits
+//                           the same bits.  --smoother=rb smooths with red-black Gauss-Seidel
+//                           (MgOpts::smoother; W then defaults to 1.0, and K counts half-sweeps);
+//                           only with --mg
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -305,6 +308,35 @@ static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const M
         }
       cur ^= 1;
     };
+    // one red-black sweep (MgOpts::smoother = 1): the red half-sweep (1-based i + j even), then the black
+    // one, each into the other buffer, which keeps every cell of the other colour
+    auto relax_rb = [&](double w) {
+      for (int colour = 0; colour < 2; ++colour) {
+        const std::vector<double>& u = v.u[cur];
+        std::vector<double>& out = v.u[cur ^ 1];
+        for (int64_t j = 1; j <= v.ny; ++j)
+          for (int64_t i = 1; i <= v.nx; ++i) {
+            const int64_t k = j * ld + i;
+            const double c = u[k];
+            if ((i + j) % 2 != colour) {
+              out[k] = c;
+              continue;
+            }
+            volatile double t = sweep(u, k) - c;
+            t = w * t;
+            out[k] = c + t;
+          }
+        cur ^= 1;
+      }
+    };
+    auto smooth = [&](int n) {
+      for (int i = 0; i < n; ++i) {
+        if (o.smoother == 1)
+          relax_rb(o.omega);
+        else
+          relax(o.omega, false);
+      }
+    };
     if (l == levels - 1) {  // Chebyshev from zero; the first iteration is the plain sweep
       double w = 1.0;
       for (int k = 0; k < coarse_iters; ++k) {
@@ -319,7 +351,7 @@ static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const M
       }
       return cur;
     }
-    for (int i = 0; i < o.nu1; ++i) relax(o.omega, false);
+    smooth(o.nu1);
     for (int64_t j = 1; j <= v.ny; ++j)
       for (int64_t i = 1; i <= v.nx; ++i) v.d[j * ld + i] = sweep(v.u[cur], j * ld + i) - v.u[cur][j * ld + i];
     Level& c = lv[l + 1];
@@ -398,7 +430,7 @@ static std::vector<double> serial_mg(int64_t ny, int64_t nx, int cycles, const M
           u[j * ld + i] = u[j * ld + i] + t;
         }
     }
-    for (int i = 0; i < o.nu2; ++i) relax(o.omega, false);
+    smooth(o.nu2);
     return cur;
   };
   int cur = 0;
@@ -507,6 +539,11 @@ int main(int argc, char** argv) {
     std::fflush(stdout);
     MPI_Abort(MPI_COMM_WORLD, 1);
   }
+  if (!mg_mode && cli.has("smoother")) {
+    if (rank == 0) std::printf("ERROR: --smoother needs --mg\n");
+    std::fflush(stdout);
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
   const bool cg_mode = cli.flag("cg") || cheby_mode || mg_mode;
   const char* mode_name = mg_mode ? "--mg" : (cheby_mode ? "--cheby" : "--cg");
   MgOpts mo;
@@ -514,7 +551,14 @@ int main(int argc, char** argv) {
   if (mg_mode) {
     const std::string nu = cli.get("nu", "2,2");
     const bool nu_ok = std::sscanf(nu.c_str(), "%d,%d", &mo.nu1, &mo.nu2) == 2;
-    mo.omega = std::atof(cli.get("omega", "0.8").c_str());
+    const std::string smoother = cli.get("smoother", "jacobi");
+    if (smoother != "jacobi" && smoother != "rb") {
+      if (rank == 0) std::printf("ERROR: --smoother must be jacobi or rb\n");
+      std::fflush(stdout);
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    mo.smoother = smoother == "rb" ? 1 : 0;
+    mo.omega = std::atof(cli.get("omega", mo.smoother ? "1.0" : "0.8").c_str());
     mo.max_levels = static_cast<int>(cli.geti("levels", 0));
     mo.coarse_iters = static_cast<int>(cli.geti("coarse-iters", 0));
     const std::string coarsen = cli.get("coarsen", "nested");
@@ -816,6 +860,7 @@ int main(int argc, char** argv) {
     const char* unit = mg_mode ? "cycle" : "iteration";
     if (cg_mode) {
       std::printf("solver    = %s\n", solver_name);
+      if (mg_mode && mo.smoother == 1) std::printf("smoother  = rb (omega %g)\n", mo.omega);
       if (cheby_mode) std::printf("rho       = %.17g%s\n", rho_used, ho.rho == 0 ? " (closed form)" : "");
       if (mg_mode) {
         std::printf("levels    = %d (coarsest %lld x %lld, %d iterations, rho %.6g)\n", mr.levels,
@@ -894,7 +939,7 @@ int main(int argc, char** argv) {
     if (mg_mode)
       j.add("solver", "multigrid").add("coarsen", mo.coarsen ? "any" : "nested").add("levels", mr.levels)
           .add("cycles", mr.iters).add("fuse", mr.fuse).add("fuse_fine", mr.fuse_fine)
-          .add("fuse_levels", mr.fuse_levels)
+          .add("fuse_levels", mr.fuse_levels).add("smoother", mo.smoother ? "rb" : "jacobi")
           .add("residual_cycles", mr.residual_iters).add("checks", mr.checks).add("converged", mr.converged != 0)
           .add("solve_ms", solve_ms).add("r0", mr.r0).add("residual_max", mr.residual_max);
     else if (cg_mode)

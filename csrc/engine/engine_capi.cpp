@@ -285,6 +285,7 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   mo.coarse_iters = o->coarse_iters;
   mo.coarsen = o->coarsen;
   mo.fuse = o->fuse;
+  mo.smoother = o->smoother;
   gmt::MgResult r;
   try {
     r = s.mg(mo);
@@ -295,7 +296,7 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   }
   *out = {r.converged, r.iters,  r.checks,    r.residual_iters, r.residual,     r.residual_max, r.r0,
           r.failed,    r.levels, r.coarse_ny, r.coarse_nx,      r.coarse_iters, r.coarse_rho,
-          r.fuse,      r.fuse_fine, r.fuse_levels};
+          r.fuse,      r.fuse_fine, r.fuse_levels, r.smoother};
   return 0;
 }
 int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,

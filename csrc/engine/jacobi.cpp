@@ -1575,16 +1575,36 @@ void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
 }
 
 // n sweeps of the smoother on level l: chunks of min(n, depth); a chunk of two
-// or more is one depth-wide exchange with corners and one gmt_mg_smooth_k
+// or more is one depth-wide exchange with corners and one gmt_mg_smooth_k.
+// Red-black: 2n half-sweeps in the same chunks, through gmt_mg_smooth_rb.
 void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o) {
   MgLevel& L = mg_[mgh_][l];
   const int64_t ldf = L.sp ? L.ld : 0;
   const double c1 = L.sp ? 1.0 : 0.0;
   const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
                    (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+  const bool rb = o.smoother == 1;
+  // cell (xo, yo) has the 1-based global indices (ox + 1, oy + 1): red, due first, iff ox + oy is even
+  int par = static_cast<int>((L.ox + L.oy) & 1);
+  if (rb) n *= 2;
   while (n > 0) {
     const int c = std::min(n, L.depth);
-    if (c >= 2) {
+    if (rb) {
+      if (c >= 2) {
+        if (mask != 0) {
+          Halo2D& h = *L.hk[L.cur][L.depth];
+          if (h.active()) {
+            h.start(s_);
+            h.finish(s_);
+          }
+        }
+      } else {
+        mg_ring(l);
+      }
+      GMT_CHECK("mg red-black smooth", gmt_mg_smooth_rb(c, par, L.xo, L.nx, L.yo, L.ny, mask, L.up[L.cur], L.ld, L.sp,
+                                                        ldf, kC0, c1, o.omega, L.up[L.cur ^ 1], L.ld, s_));
+      par ^= c & 1;
+    } else if (c >= 2) {
       // a rank without neighbours reads its fixed ring only
       if (mask != 0) {
         Halo2D& h = *L.hk[L.cur][L.depth];
@@ -1679,9 +1699,10 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
                        o.check_every == 0 ? 1 : o.check_every, o.lag, false};
   loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
                     o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1) &&
-                    (o.fuse == 0 || (o.fuse >= 2 && o.fuse <= GMT_MG_MAX_FUSE)),
+                    (o.fuse == 0 || (o.fuse >= 2 && o.fuse <= GMT_MG_MAX_FUSE)) &&
+                    (o.smoother == 0 || o.smoother == 1),
                 ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0, "
-                "coarsen 0 or 1, fuse 0 or 2..4");
+                "coarsen 0 or 1, fuse 0 or 2..4, smoother 0 or 1");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
   const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels, o.coarsen);
@@ -1707,6 +1728,7 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   F.sp = src_f();
   mg_fuse_setup(levels, o);
   res.fuse = o.fuse;
+  res.smoother = o.smoother;
   res.fuse_fine = F.depth;
   for (int l = 0; l + 1 < levels; ++l) res.fuse_levels += mg_[mgh_][l].depth >= 2;
   F.cur = parity_;

@@ -480,9 +480,10 @@ int gmt_mg_smooth_k_path(int, int64_t, int64_t, int64_t, int, const double*, int
   return GMT_PATH_NONE;
 }
 
-int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u, int64_t ld,
-                    const double* f, int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo,
-                    void*) {
+// rb: only the cells due in half-sweep j are updated (gmt_mg_smooth_rb's colour rule)
+static int mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
+                            const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
+                            double omega, double* out, int64_t ldo) {
   if (k < 1 || k > GMT_MG_MAX_FUSE || halo_mask < 0 || halo_mask > 15) return 1;
   if (nx < 0 || ny < 0) return 1;
   if (nx == 0 || ny == 0) return 0;
@@ -511,6 +512,11 @@ int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int h
     for (int64_t y = by0; y < by1; ++y)
       for (int64_t x = bx0; x < bx1; ++x) {
         const double* c = w.data() + y * wx + x;
+        // (x - gw) + (y - gs) is the offset from cell (x0, y0); & 1 is the mathematical mod
+        if (rb && (((x - gw) + (y - gs) + par + (j - 1)) & 1) != 0) {
+          t[y * wx + x] = c[0];
+          continue;
+        }
         double o = c0 * ((c[-1] + c[1]) + (c[-wx] + c[wx]));
         if (f) o = o + c1 * f[(y0 - gs + y) * ldf + (x0 - gw + x)];
         const double d = o - c[0];
@@ -523,6 +529,26 @@ int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int h
   for (int64_t y = 0; y < ny; ++y)
     for (int64_t x = 0; x < nx; ++x) out[(y0 + y) * ldo + x0 + x] = w[(gs + y) * wx + gw + x];
   return 0;
+}
+
+int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u, int64_t ld,
+                    const double* f, int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo,
+                    void*) {
+  return mg_smooth_levels(k, false, 0, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
+}
+
+// h coloured half-sweeps: the same definition with the colour rule
+int gmt_mg_smooth_rb_path(int, int, int64_t, int64_t, int64_t, int, const double*, int64_t, const double*, int64_t,
+                          const double*, int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u,
+                     int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
+                     int64_t ldo, void*) {
+  if (par < 0 || par > 1) return 1;
+  return mg_smooth_levels(h, true, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
 }
 
 int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* d, int64_t ldd,

@@ -137,6 +137,7 @@ typedef struct gmt_engine_mg_opts {
   int coarse_iters; /* 0 = gmt_engine_mg_coarse_iters(rho of the coarsest level) */
   int coarsen;      /* 0 nested (nx + 1 and ny + 1 even on every level), 1 any lattice size (MgOpts::coarsen) */
   int fuse;         /* 0, or 2..4: sweeps of a smoothing run per memory pass (MgOpts::fuse) */
+  int smoother;     /* 0 damped Jacobi, 1 red-black Gauss-Seidel (MgOpts::smoother); omega is taken as given */
 } gmt_engine_mg_opts;
 typedef struct gmt_engine_mg_result {
   int converged, iters, checks, residual_iters;
@@ -147,6 +148,7 @@ typedef struct gmt_engine_mg_result {
   int coarse_iters;
   double coarse_rho;
   int fuse, fuse_fine, fuse_levels; /* as requested; the depth of level 0; levels with a depth >= 2 */
+  int smoother;                     /* as requested */
 } gmt_engine_mg_result;
 /* 0; 1 on invalid options, 2 on an engine with a periodic axis, 3 when the
  * problem has no coarse level: nx + 1 or ny + 1 odd, 4 when a rank of the

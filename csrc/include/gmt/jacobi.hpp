@@ -234,6 +234,7 @@ struct MgOpts {
   int coarse_iters = 0;          // Chebyshev iterations on the coarsest level (0 = mg_coarse_iters(rho))
   int coarsen = 0;               // 0 nested; 1 any: every lattice size (both above)
   int fuse = 0;                  // 0, or 2..GMT_MG_MAX_FUSE: sweeps of a smoothing run per memory pass (below)
+  int smoother = 0;              // 0 damped Jacobi; 1 red-black Gauss-Seidel (below)
 };
 struct MgResult : CheckResult {
   int levels = 0;                          // levels used, the fine one included
@@ -243,6 +244,7 @@ struct MgResult : CheckResult {
   int fuse = 0;                            // MgOpts::fuse as requested
   int fuse_fine = 1;                       // the depth of level 0 (1: it smooths sweep by sweep)
   int fuse_levels = 0;                     // smoothing levels with a depth >= 2
+  int smoother = 0;                        // MgOpts::smoother as requested
 };
 // MgOpts::fuse > 0 runs the sweeps of a smoothing run through gmt_mg_smooth_k,
 // up to `fuse` of them per memory pass, for the same bits.  Every smoothing
@@ -259,6 +261,16 @@ struct MgResult : CheckResult {
 // on coarse levels, once per source on level 0.  The coarse levels of such a
 // call have GMT_MG_MAX_FUSE ghost rows and columns (one hierarchy per coarsen
 // mode, built apart from the fuse = 0 ones, whose layout is unchanged).
+// MgOpts::smoother = 1 smooths with red-black Gauss-Seidel (gmt_mg_smooth_rb).
+// A cell of a level is red iff the sum of its 1-based global indices on that
+// level's lattice is even; a sweep is the red half-sweep, then the black one
+// (omega is the cell's, 1.0 for plain Gauss-Seidel).  A run of n sweeps is 2n
+// half-sweeps in the chunks above with half-sweeps for sweeps: a chunk of two
+// or more is one d_l-wide exchange with corners and one gmt_mg_smooth_rb, a
+// chunk of one the 1-wide faces-only exchange and one launch with h = 1.  par
+// comes from the rank's global offset on the level and the half-sweeps the run
+// has done, so the field does not depend on the process grid.  Depths, halo
+// plans, source rings, residual, transfers and the coarsest level are the same.
 // The depth of each smoothing level (the coarsest level has none).
 std::vector<int> mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
                                 int coarsen);

@@ -379,6 +379,31 @@ int gmt_mg_smooth_k_path(int k, int64_t x0, int64_t nx, int64_t ny, int halo_mas
  * (either pointer may be NULL); non-zero for k outside 1..GMT_MG_MAX_FUSE. */
 int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols);
 
+/* ---- h coloured half-sweeps of red-black Gauss-Seidel in one memory pass:
+ *      gmt_mg_smooth_k with h for k and a colour rule on top.  par in {0, 1} is
+ *      the colour phase of cell (x0, y0): in half-sweep j (1-based) cell (x, y)
+ *      is due iff (x - x0) + (y - y0) + par + (j - 1) is even (a mathematical
+ *      mod: the offsets are negative on halo sides).
+ *      B_j = R grown by h - j on halo sides, by 0 on ring sides; U_0 = u;
+ *      U_j = gmt_mg_smooth's cell of U_{j-1} (no contraction, the same order)
+ *      on the due cells of B_j and U_{j-1} on every other cell; out[R] = U_h.
+ *      Two consecutive half-sweeps are one red-black sweep, so h = 2 is one
+ *      sweep and h = 4 two of them, still 16 B per point (24 with f).
+ *      The read sets of u and f, the cells written, the empty region, the
+ *      overlap rule and the refusals are gmt_mg_smooth_k's with h for k; par
+ *      outside 0..1 is refused too.  The fast path (the alignment rule of
+ *      gmt_mg_smooth) is the k-level row walk with k = h, h = 1 included, in
+ *      the geometry of gmt_mg_smooth_k_geom(h): the lane's pair starts on an
+ *      even region-relative column, so which cell of a pair is due is a scalar
+ *      per row.  Other arguments take the one-lane-per-cell kernel.
+ *      _path: as gmt_mg_smooth_k_path. */
+int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u,
+                     int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
+                     int64_t ldo, void* stream);
+int gmt_mg_smooth_rb_path(int h, int par, int64_t x0, int64_t nx, int64_t ny, int halo_mask, const double* u,
+                          int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo,
+                          int64_t* seg_rows);
+
 /* ---- Table-driven transfers between two levels that are not nested: n fine
  *      and m coarse interior points per axis on the same interval (any m with
  *      3 or 4 fine points between the neighbours of a coarse one), linear

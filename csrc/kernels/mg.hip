@@ -149,6 +149,14 @@ static int mg_smooth_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64
 //   mg_smooth_k_scalar  one lane per output cell: the cells of its dependence
 //                       cone (|dx| + |dy| <= K - j at level j) level by level
 //                       in registers, with the same cell and keep rule.
+//   red-black (gmt_mg_smooth_rb): the same two kernels with RB set and K = h
+//                       half-sweeps, K = 1 included.  Level l + 1 updates only
+//                       the cells that are due in half-sweep l + 1; in the walk
+//                       that is one scalar per arriving row (see there), folded
+//                       into the select, so the pass stays at 16 B/pt.  Both
+//                       cells of a pair are evaluated and one is discarded:
+//                       evaluating the due cell alone, operands by selects,
+//                       measured the same (profiles/mg_rb).
 
 constexpr int kMgMaxFuse = GMT_MG_MAX_FUSE;
 // the shortest segment: 4k rows rounded up to a power of two, so the 2k warm-up
@@ -171,11 +179,12 @@ struct MgFuseArgs {
   double* out;
   int64_t ldo;
   int64_t nseg, seg_rows, nblocks;
+  int par;  // red-black only: the colour phase of cell (x0, y0)
 };
 
 __device__ __forceinline__ int64_t mg_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-template <int K, bool HAS_F>
+template <int K, bool HAS_F, bool RB = false>
 __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
   constexpr int SH = mg_fuse_shift(K), OC = mg_fuse_wave_cols(K);
   constexpr int U = HAS_F ? kMgUnrollF : kMgUnrollP;
@@ -255,6 +264,9 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
         fh[0] = fn[j];
       }
       d2 C = cn[j];
+      // red-black: level l + 1 is half-sweep l + 1 on row tr - 1 - l, and the lane's pair starts on an even
+      // column, so which cell of the pair is due is one scalar for the row that arrives, the same at every level
+      const bool duex = !RB || ((tr - 1 + a.par) & 1) == 0, duey = !RB || !duex;
 #pragma unroll
       for (int l = 0; l < K; ++l) {
         const int64_t y = tr - 1 - l;
@@ -265,8 +277,8 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
         d2 n;
         n.x = mg_smooth_cell<HAS_F>(w, b.y, A[l].x, C.x, b.x, a.c0, a.c1, fh[l].x, a.om);
         n.y = mg_smooth_cell<HAS_F>(b.x, e, A[l].y, C.y, b.y, a.c0, a.c1, fh[l].y, a.om);
-        n.x = rok && mx[l] ? n.x : b.x;
-        n.y = rok && my[l] ? n.y : b.y;
+        n.x = rok && duex && mx[l] ? n.x : b.x;
+        n.y = rok && duey && my[l] ? n.y : b.y;
         A[l] = b;
         B[l] = C;
         C = n;
@@ -285,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
   }
 }
 
-template <int K, bool HAS_F>
+template <int K, bool HAS_F, bool RB = false>
 __global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgFuseArgs a) {
   const double* __restrict__ u = a.u;
   const double* __restrict__ f = a.f;
@@ -320,7 +332,8 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgFuseArgs a)
           const int64_t X = x + dx, Y = y + dy;
           const double cv = v[dy + K][dx + K];
           double r = cv;
-          if (X >= bxl && X < bxh && Y >= byl && Y < byh)
+          const bool due = !RB || ((X + Y + a.par + (j - 1)) & 1) == 0;  // two's complement: the mathematical mod
+          if (due && X >= bxl && X < bxh && Y >= byl && Y < byh)
             r = mg_smooth_cell<HAS_F>(v[dy + K][dx + K - 1], v[dy + K][dx + K + 1], v[dy + K - 1][dx + K],
                                       v[dy + K + 1][dx + K], cv, a.c0, a.c1, HAS_F ? fb[Y * a.ldf + X] : 0.0, a.om);
           n[dy + K][dx + K] = r;
@@ -358,7 +371,7 @@ static bool mg_fuse_args_ok(int k, int64_t x0, int64_t nx, int64_t y0, int64_t n
   return !(ua < oe && oa < ub);
 }
 
-template <int K, bool HAS_F>
+template <int K, bool HAS_F, bool RB = false>
 static int mg_smooth_k_launch(bool walk, MgFuseArgs a, hipStream_t s) {
   if (walk) {
     const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(K)) * (kBlock / kWave);
@@ -366,18 +379,18 @@ static int mg_smooth_k_launch(bool walk, MgFuseArgs a, hipStream_t s) {
     a.nseg = (a.ny + a.seg_rows - 1) / a.seg_rows;
     a.nblocks = (a.nx + bc - 1) / bc * a.nseg;
     if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
-    mg_smooth_k_walk<K, HAS_F><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
+    mg_smooth_k_walk<K, HAS_F, RB><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
   } else {
     const int64_t nb = (a.nx * a.ny + kBlock - 1) / kBlock;
     if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_smooth_k_scalar<K, HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(a);
+    mg_smooth_k_scalar<K, HAS_F, RB><<<grid_1d(nb), kBlock, 0, s>>>(a);
   }
   GMT_RET_LAUNCH();
 }
 
-template <int K>
+template <int K, bool RB = false>
 static int mg_smooth_k_launch_f(bool walk, const MgFuseArgs& a, hipStream_t s) {
-  return a.f ? mg_smooth_k_launch<K, true>(walk, a, s) : mg_smooth_k_launch<K, false>(walk, a, s);
+  return a.f ? mg_smooth_k_launch<K, true, RB>(walk, a, s) : mg_smooth_k_launch<K, false, RB>(walk, a, s);
 }
 
 // ---- full weighting ----
@@ -716,11 +729,43 @@ extern "C" int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_
     return static_cast<int>(hipErrorInvalidValue);
   if (k == 1) return gmt_mg_smooth(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, stream);
   const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
-  const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0};
+  const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0, 0};
   switch (k) {
     case 2: return mg_smooth_k_launch_f<2>(walk, a, s);
     case 3: return mg_smooth_k_launch_f<3>(walk, a, s);
     default: return mg_smooth_k_launch_f<4>(walk, a, s);
+  }
+}
+
+extern "C" int gmt_mg_smooth_rb_path(int h, int par, int64_t x0, int64_t nx, int64_t ny, int halo_mask,
+                                     const double* u, int64_t ld, const double* f, int64_t ldf, const double* out,
+                                     int64_t ldo, int64_t* seg_rows) {
+  using namespace gmt;
+  if (seg_rows) *seg_rows = 0;
+  if (h < 1 || h > kMgMaxFuse || par < 0 || par > 1 || halo_mask < 0 || halo_mask > 15) return GMT_PATH_NONE;
+  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);
+  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(h, nx, ny);
+  return path;
+}
+
+extern "C" int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
+                                const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
+                                double omega, double* out, int64_t ldo, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (h < 1 || h > kMgMaxFuse || par < 0 || par > 1 || halo_mask < 0 || halo_mask > 15)
+    return static_cast<int>(hipErrorInvalidValue);
+  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
+  if (nx == 0 || ny == 0) return 0;
+  if (!mg_fuse_args_ok(h, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo))
+    return static_cast<int>(hipErrorInvalidValue);
+  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
+  const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0, par};
+  switch (h) {
+    case 1: return mg_smooth_k_launch_f<1, true>(walk, a, s);  // the K-level walk with one level: 16 B per point
+    case 2: return mg_smooth_k_launch_f<2, true>(walk, a, s);
+    case 3: return mg_smooth_k_launch_f<3, true>(walk, a, s);
+    default: return mg_smooth_k_launch_f<4, true>(walk, a, s);
   }
 }
 

@@ -185,6 +185,13 @@ _SIGS = {
     "gmt_mg_smooth_k_path": (
         c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_mg_smooth_k_geom": (c_int, [c_int, c_vp, c_vp]),
+    "gmt_mg_smooth_rb": (
+        c_int,
+        [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64,
+         c_vp],
+    ),
+    "gmt_mg_smooth_rb_path": (
+        c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "gmt_mg_restrict": (
         c_int,
         [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_dbl, c_vp, c_i64, c_i64, c_i64, c_vp],

@@ -104,7 +104,7 @@ class MgOpts(ctypes.Structure):
                 ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
                 ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
                 ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int),
-                ("fuse", ctypes.c_int)]
+                ("fuse", ctypes.c_int), ("smoother", ctypes.c_int)]
 
 
 class MgResult(ctypes.Structure):
@@ -114,11 +114,21 @@ class MgResult(ctypes.Structure):
                 ("residual_max", ctypes.c_double), ("r0", ctypes.c_double), ("failed", ctypes.c_int),
                 ("levels", ctypes.c_int), ("coarse_ny", ctypes.c_int64), ("coarse_nx", ctypes.c_int64),
                 ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double),
-                ("fuse", ctypes.c_int), ("fuse_fine", ctypes.c_int), ("fuse_levels", ctypes.c_int)]
+                ("fuse", ctypes.c_int), ("fuse_fine", ctypes.c_int), ("fuse_levels", ctypes.c_int),
+                ("smoother", ctypes.c_int)]
 
 
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
 COARSEN = {"nested": 0, "any": 1}  # MgOpts::coarsen
+SMOOTHERS = {"jacobi": 0, "rb": 1}  # MgOpts::smoother
+MG_OMEGA = {"jacobi": 0.8, "rb": 1.0}  # the damping when the caller gives none
+
+
+def _mg_smoother(smoother, omega):
+    """``(smoother, omega)`` checked, with the smoother's default damping for ``omega=None``."""
+    if not isinstance(smoother, str) or smoother not in SMOOTHERS:
+        raise ValueError(f"smoother must be one of {sorted(SMOOTHERS)}, got {smoother!r}")
+    return smoother, MG_OMEGA[smoother] if omega is None else float(omega)
 MG_MAX_FUSE = 4  # GMT_MG_MAX_FUSE: the largest MgOpts::fuse
 CG_CHECK_EVERY = 10  # CgOpts::check_every == 0
 MAX_LAG = 8
@@ -692,8 +702,8 @@ class NativeJacobi:
         return {n: getattr(r, n) for n, _ in ChebyResult._fields_}
 
     def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
-           lag: int = 1, nu: tuple = (2, 2), omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0,
-           coarsen: str = "nested", fuse: int = 0) -> dict:
+           lag: int = 1, nu: tuple = (2, 2), omega: "float | None" = None, max_levels: int = 0,
+           coarse_iters: int = 0, coarsen: str = "nested", fuse: int = 0, smoother: str = "jacobi") -> dict:
         """Geometric multigrid V-cycles from the current field
         (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
         ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
@@ -715,7 +725,16 @@ class NativeJacobi:
         ``converged``, ``iters`` (cycles), ``checks``, ``residual_iters``,
         ``residual``, ``residual_max``, ``r0``, ``failed``, ``levels``,
         ``coarse_ny``, ``coarse_nx``, ``coarse_iters``, ``coarse_rho``,
-        ``fuse``, ``fuse_fine``, ``fuse_levels``.
+        ``fuse``, ``fuse_fine``, ``fuse_levels``, and ``smoother`` and ``omega``
+        as used.
+        ``smoother="rb"`` smooths with red-black Gauss-Seidel
+        (gmt_mg_smooth_rb) instead of damped Jacobi: a cell is red iff the sum
+        of its 1-based global indices on its level is even, a sweep is the red
+        half-sweep then the black one, each ``u + omega*(G(u) - u)`` on its
+        colour.  ``omega=None`` is 0.8 for ``"jacobi"`` and 1.0 for ``"rb"``.
+        Under ``fuse`` a run of ``n`` sweeps is ``2n`` half-sweeps, up to
+        ``fuse`` of them per memory pass; ``fuse=0`` runs each half-sweep behind
+        its own exchange.
         ``fuse`` (0, or 2..4) runs up to that many sweeps of a smoothing run in
         one memory pass (gmt_mg_smooth_k) behind one exchange as wide, for the
         same bits: every level has the depth :func:`mg_fuse_depths` gives it (a
@@ -735,7 +754,8 @@ class NativeJacobi:
             raise ValueError(f"check_every must be >= 1 (0 = 1), got {check_every!r}")
         if int(max_cycles) < 1 or int(max_cycles) % every:
             raise ValueError(f"max_cycles must be a positive multiple of check_every ({every}), got {max_cycles!r}")
-        tol, rtol, omega = float(tol), float(rtol), float(omega)
+        smoother, omega = _mg_smoother(smoother, omega)
+        tol, rtol = float(tol), float(rtol)
         if not (np.isfinite(tol) and np.isfinite(rtol)) or tol < 0 or rtol < 0:
             raise ValueError("tol and rtol must be finite and >= 0")
         nu1, nu2 = (int(v) for v in nu)
@@ -751,7 +771,7 @@ class NativeJacobi:
             raise ValueError(f"fuse must be 0 or 2..{MG_MAX_FUSE}, got {fuse!r}")
         o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
                    nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters),
-                   coarsen=COARSEN[coarsen], fuse=int(fuse))
+                   coarsen=COARSEN[coarsen], fuse=int(fuse), smoother=SMOOTHERS[smoother])
         r = MgResult()
         rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
         if rc == 2:
@@ -763,7 +783,10 @@ class NativeJacobi:
                 "the extents are too small or a rank of the process grid would own no coarse point"))
         if rc:
             raise ValueError("gmt_engine_jacobi_mg rejected its options")
-        return {n: getattr(r, n) for n, _ in MgResult._fields_}
+        out = {n: getattr(r, n) for n, _ in MgResult._fields_}
+        out["smoother"] = smoother
+        out["omega"] = omega
+        return out
 
     def interior(self) -> np.ndarray:
         out = np.empty((self.ny, self.nx), dtype=np.float64)
@@ -1204,14 +1227,18 @@ def mg_fuse_depths(ny: int, nx: int, dims: tuple, fuse: int, ghost: int, max_lev
 
 def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int = 0,
               source: "str | np.ndarray | None" = None, source_amp: float = 1.0, nu: tuple = (2, 2),
-              omega: float = 0.8, max_levels: int = 0, coarse_iters: int = 0, coarse_rho: "float | None" = None,
-              keep=None, start: "np.ndarray | None" = None, coarsen: str = "nested"):
+              omega: "float | None" = None, max_levels: int = 0, coarse_iters: int = 0,
+              coarse_rho: "float | None" = None, keep=None, start: "np.ndarray | None" = None,
+              coarsen: str = "nested", smoother: str = "jacobi"):
     """NumPy definition of :meth:`NativeJacobi.mg` on the whole Dirichlet
     problem: ``cycles`` V-cycles from the engine's initial field, every cell in
     the kernels' operation order (ops/reference.py ``mg_smooth``,
     ``mg_restrict``, ``mg_prolong_add``, and with ``coarsen="any"`` on a level
     with an even extent ``mg_restrict_tab``, ``mg_prolong_add_tab``; the
     coarsest level as :func:`serial_cheby` from zero) — bitwise the engine's field.
+    ``smoother="rb"``: every smoothing sweep is ``mg_smooth_rb(h=2, par=0)`` over
+    the whole level, whose first interior cell is red.  ``omega=None`` is 0.8
+    for ``"jacobi"`` and 1.0 for ``"rb"``.
     ``coarse_rho``: the coarsest level's spectral radius (default
     :func:`cheby_rho`; the engine reports the value it used).  ``start``: an
     ny x nx interior to start from inside the initial field's ring, as a call
@@ -1227,6 +1254,14 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
         raise ValueError("mg: no coarse level: " + ("nx + 1 and ny + 1 must be even" if coarsen == "nested" else
                                                     "the extents leave no coarse point"))
     nu1, nu2 = (int(v) for v in nu)
+    smoother, omega = _mg_smoother(smoother, omega)
+
+    def smooth(a, b, n, m, f):
+        if smoother == "rb":
+            ref.mg_smooth_rb(a, b, omega, 1, n, 1, m, 2, 0, 0, f, 0.25, 1.0)
+        else:
+            ref.mg_smooth(a, b, omega, 1, n, 1, m, f, 0.25, 1.0)
+
     rho = cheby_rho(*levels[-1]) if coarse_rho is None else float(coarse_rho)
     citers = int(coarse_iters) or mg_coarse_iters(rho)
     weights = cheby_weights(rho, citers)
@@ -1259,7 +1294,7 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
                 cur ^= 1
             return cur
         for _ in range(nu1):
-            ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
+            smooth(u[cur], u[cur ^ 1], n, m, f)
             cur ^= 1
         a = u[cur]
         D[lv][2:-2, 2:-2] = sweep(a, f) - a[1:-1, 1:-1]
@@ -1277,7 +1312,7 @@ def serial_mg(ny: int, nx: int, cycles: int, init: str = "analytic", seed: int =
         else:
             ref.mg_prolong_add(U[lv + 1][c], a, 1, n, 1, m, 1, 1, 1, 1)
         for _ in range(nu2):
-            ref.mg_smooth(u[cur], u[cur ^ 1], omega, 1, n, 1, m, f, 0.25, 1.0)
+            smooth(u[cur], u[cur ^ 1], n, m, f)
             cur ^= 1
         return cur
 

@@ -9,7 +9,8 @@ its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
 ``cg_apply`` / ``cg_update`` / ``cg_dir``, the Chebyshev step ``cheby_step``,
 the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
 ``mg_prolong_add``, the fused smoother ``mg_smooth_k`` (k sweeps per memory
-pass), the table-driven transfers for levels that are not nested
+pass), the red-black Gauss-Seidel smoother ``mg_smooth_rb`` (h coloured
+half-sweeps per memory pass), the table-driven transfers for levels that are not nested
 ``mg_restrict_tab`` / ``mg_prolong_add_tab``, and ``jacobi5tb`` (K fused sweeps
 per memory pass).
 """
@@ -56,6 +57,8 @@ from .kernels import (  # noqa: F401
     mg_smooth_k_geom,
     mg_smooth_k_path,
     mg_smooth_path,
+    mg_smooth_rb,
+    mg_smooth_rb_path,
     jacobi5xk,
     jacobi5tb,
     jacobi5tb_plan,

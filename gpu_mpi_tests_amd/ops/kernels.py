@@ -658,6 +658,43 @@ def mg_smooth_k_geom(k: int) -> tuple[int, int]:
     return int(wc.value), int(bc.value)
 
 
+def mg_smooth_rb(u: torch.Tensor, out: torch.Tensor, omega: float, region: tuple[int, int, int, int], h: int,
+                 par: int, halo_mask: int = 0, f: torch.Tensor | None = None, c0: float = 0.25,
+                 c1: float = 1.0) -> torch.Tensor:
+    """``h`` (1..4) coloured half-sweeps of red-black Gauss-Seidel over
+    ``region`` in one memory pass (gmt_mg_smooth_rb): :func:`mg_smooth_k` with
+    ``h`` for ``k``, where half-sweep ``j`` updates only the cells whose offset
+    from the region's first cell has ``dx + dy + par + (j - 1)`` even.  Two
+    half-sweeps are one red-black sweep.  Bitwise
+    :func:`reference.mg_smooth_rb`.  ``u`` and ``out`` must not share storage.
+    Returns ``out``."""
+    _check2d(u, "mg_smooth_rb.u")
+    _check2d(out, "mg_smooth_rb.out")
+    if f is not None:
+        _check2d(f, "mg_smooth_rb.f")
+    if _overlap(u, out):
+        raise ValueError("mg_smooth_rb: u and out must not share storage")
+    x0, nx, y0, ny = (int(t) for t in region)
+    if not _is_dev(out):
+        return ref.mg_smooth_rb(u, out, omega, x0, nx, y0, ny, int(h), int(par), int(halo_mask), f, c0, c1)
+    _native.check(_native.lib().gmt_mg_smooth_rb(int(h), int(par), x0, nx, y0, ny, int(halo_mask), u.data_ptr(),
+                                                 u.stride(0), *_ptr_ld(f), float(c0), float(c1), float(omega),
+                                                 out.data_ptr(), out.stride(0), _stream(out)), "gmt_mg_smooth_rb")
+    return out
+
+
+def mg_smooth_rb_path(u: torch.Tensor, out: torch.Tensor, region: tuple[int, int, int, int], h: int, par: int = 0,
+                      halo_mask: int = 0, f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`mg_smooth_rb` would launch (gmt_mg_smooth_rb_path, no
+    launch): ``(PATH_ROW_WALK or PATH_SCALAR, output rows per segment of the walk)``."""
+    x0, nx, _, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_mg_smooth_rb_path(int(h), int(par), x0, nx, ny, int(halo_mask), u.data_ptr(),
+                                               u.stride(0), *_ptr_ld(f), out.data_ptr(), out.stride(0),
+                                               ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
 def mg_restrict(d: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
                 coarse: tuple[int, int], cs: float = 0.25) -> torch.Tensor:
     """Full weighting of the fine field ``d`` over ``region = (x0, nx, y0, ny)``

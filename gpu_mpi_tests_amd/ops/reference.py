@@ -220,6 +220,43 @@ def mg_smooth_k(u, out, omega: float, x0: int, nx: int, y0: int, ny: int, k: int
     return out
 
 
+def mg_smooth_rb(u, out, omega: float, x0: int, nx: int, y0: int, ny: int, h: int, par: int, halo_mask: int = 0,
+                 f=None, c0: float = 0.25, c1: float = 1.0):
+    """gmt_mg_smooth_rb: ``h`` coloured half-sweeps over a copy of ``u``.  The
+    j-th is :func:`mg_smooth` on the box of :func:`mg_smooth_k` (``h`` for
+    ``k``), merged through the colour mask: cell (x, y) takes the new value iff
+    ``(x - x0) + (y - y0) + par + (j - 1)`` is even and keeps its own otherwise.
+    ``out[region]`` gets the last one.  Works on torch tensors and NumPy arrays
+    alike."""
+    if not 1 <= h <= MG_MAX_FUSE or not 0 <= halo_mask <= 15 or par not in (0, 1):
+        raise ValueError("mg_smooth_rb: h outside 1..4, a mask outside 0..15 or par outside 0..1")
+    if nx < 0 or ny < 0:
+        raise ValueError("mg_smooth_rb: negative extent")
+    if nx > 0 and ny > 0:
+        tensor = hasattr(u, "clone")
+        a = u.clone() if tensor else u.copy()
+        b = u.clone() if tensor else u.copy()
+        for j in range(1, h + 1):
+            g = h - j
+            gw, ge = (g if halo_mask & MG_HALO_W else 0), (g if halo_mask & MG_HALO_E else 0)
+            gs, gn = (g if halo_mask & MG_HALO_S else 0), (g if halo_mask & MG_HALO_N else 0)
+            bx, by, bnx, bny = x0 - gw, y0 - gs, nx + gw + ge, ny + gs + gn
+            mg_smooth(a, b, omega, bx, bnx, by, bny, f, c0, c1)
+            if tensor:
+                import torch
+
+                xs, ys = torch.arange(bx, bx + bnx), torch.arange(by, by + bny)
+            else:
+                import numpy as np
+
+                xs, ys = np.arange(bx, bx + bnx), np.arange(by, by + bny)
+            due = ((xs - x0)[None, :] + (ys - y0)[:, None] + (par + j - 1)) % 2 == 0  # % is the mathematical mod
+            box = a[by : by + bny, bx : bx + bnx]
+            box[due] = b[by : by + bny, bx : bx + bnx][due]
+        out[y0 : y0 + ny, x0 : x0 + nx] = a[y0 : y0 + ny, x0 : x0 + nx]
+    return out
+
+
 def mg_coarse_extent(n: int, p: int) -> int:
     """Coarse cells of a fine region of n cells whose first coarse point has the region-relative index p."""
     return (n - p + 1) // 2
