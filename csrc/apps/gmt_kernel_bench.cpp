@@ -28,7 +28,9 @@
 //      f, compared bitwise with k single sweeps and timed beside them and DAXPY,
 //      and the red-black smoother gmt_mg_smooth_rb for h = 1, 2, 4 half-sweeps
 //      without and with f, compared bitwise with h launches of h = 1 and timed
-//      beside gmt_mg_smooth_k of k = h
+//      beside gmt_mg_smooth_k of k = h, and the fused transfer
+//      gmt_mg_resid_restrict without and with f, compared bitwise with
+//      gmt_cg_apply mode 1 + gmt_mg_restrict and timed beside the two
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -693,6 +695,60 @@ int main(int argc, char** argv) {
           std::printf("mg %lldx%lld  %s ms / %s ms = %.4f  (best of %d)\n", (long long)n, (long long)n, nm, nmk,
                       st[0].min() / st[1].min(), reps);
         }
+    }
+    {
+      // the fused transfer (gmt_mg_resid_restrict, mask 0) without and with f: first compared bitwise with
+      // gmt_cg_apply mode 1 into a field whose ring is zero followed by gmt_mg_restrict, then timed beside those
+      // two launches in the order A B B A.  The byte model per fine point: 8 + 2 against 16 + 10 (16 + 2 against
+      // 24 + 10 with f).
+      Buffer<double> d(elems, GMT_SPACE_DEVICE), e2(celems, GMT_SPACE_DEVICE);
+      Buffer<double> cws(static_cast<size_t>(gmt_cg_workspace(n, n)) + 2, GMT_SPACE_DEVICE);
+      Buffer<double> dws(static_cast<size_t>(2 * gmt_diff_sq_workspace(m, m)) + 2, GMT_SPACE_DEVICE);
+      GMT_CHECK("memset", gmt_rt_memset_async(d.data(), 0, d.bytes(), s));
+      GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, u.data(), ld, s));
+      for (int wf = 0; wf < 2; ++wf) {
+        const double* fp = wf ? f.data() : nullptr;
+        const int64_t ldf = wf ? ld : 0;
+        const double c1 = wf ? 1.0 : 0.0;
+        const char* nm = wf ? "mg_resid_restrict_f" : "mg_resid_restrict";
+        const char* nmp = wf ? "cg_apply+restrict_f" : "cg_apply+restrict";
+        const std::function<void()> fused = [&] {
+          GMT_CHECK(nm, gmt_mg_resid_restrict(xo, n, 1, n, 1, 1, 0, u.data(), ld, fp, ldf, 0.25, c1, 0.25, e.data(), xo,
+                                              1, ldc, s));
+        };
+        const std::function<void()> pair = [&] {
+          GMT_CHECK(nmp, gmt_cg_apply(1, xo, n, 1, n, u.data(), ld, fp, ldf, 0.25, c1, d.data(), ld, cws.data(),
+                                      cws.data() + 2, s));
+          GMT_CHECK(nmp, gmt_mg_restrict(xo, n, 1, n, 1, 1, d.data(), ld, 0.25, e2.data(), xo, 1, ldc, s));
+        };
+        int64_t segr = 0;
+        const int pr = gmt_mg_resid_restrict_path(xo, n, 1, n, 1, 1, 0, u.data(), ld, fp, ldf, e.data(), xo, 1, ldc, &segr);
+        fused();
+        pair();
+        GMT_CHECK("diff", gmt_diff_bits(m, m, e.data() + ldc + xo, ldc, e2.data() + ldc + xo, ldc, dws.data(),
+                                        dws.data() + 2, s));
+        double dres[2] = {-1.0, -1.0};
+        GMT_CHECK("D2H", gmt_rt_memcpy_async(dres, dws.data(), sizeof(dres), s));
+        GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+        std::printf("mg %lldx%lld  %s path %d (%lld rows per segment), %s bitwise cg_apply + mg_restrict: %s\n",
+                    (long long)n, (long long)n, nm, pr, (long long)segr, nm, dres[1] == 0.0 ? "yes" : "NO");
+        if (dres[1] != 0.0) return 1;
+        Stats st[2];
+        const int order[4] = {0, 1, 1, 0};
+        for (int rep = 0; rep < reps; ++rep)
+          for (int o = 0; o < 4; ++o) {
+            const double ms = time_ms(s, iters, order[o] == 0 ? fused : pair);
+            st[order[o]].add(ms);
+            std::printf("mg %lldx%lld rep %d  %-18s %9.4f ms\n", (long long)n, (long long)n, rep,
+                        order[o] == 0 ? nm : nmp, ms);
+          }
+        char shape[64];
+        std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+        report(nm, 0, shape, st[0].min(), (wf ? 18.0 : 10.0) * n * n);
+        report(nmp, 0, shape, st[1].min(), (wf ? 34.0 : 26.0) * n * n);
+        std::printf("mg %lldx%lld  %s ms / (cg_apply + mg_restrict) ms = %.4f, bytes model %s  (best of %d)\n",
+                    (long long)n, (long long)n, nm, st[0].min() / st[1].min(), wf ? "18/34" : "10/26", reps);
+      }
     }
     if (nt % 2 == 0) {
       // the general transfers on nt x nt: d with room for a 2-wide ring (interior origin (8, 2)), the same

@@ -59,7 +59,7 @@
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
 //   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any] [--fuse=K]
-//        [--smoother=jacobi|rb]
+//        [--smoother=jacobi|rb] [--fuse-resid]
 //                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
 //                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
 //                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
@@ -71,7 +71,9 @@
 //                           up to K sweeps of a smoothing run in one memory pass (MgOpts::fuse) for
 //                           the same bits.  --smoother=rb smooths with red-black Gauss-Seidel
 //                           (MgOpts::smoother; W then defaults to 1.0, and K counts half-sweeps);
-//                           only with --mg
+//                           only with --mg.  --fuse-resid computes the residual and its restriction
+//                           in one memory pass on every level that allows it (MgOpts::fuse_resid)
+//                           for the same bits
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
 #include <mpi.h>
@@ -569,6 +571,7 @@ int main(int argc, char** argv) {
     }
     mo.coarsen = coarsen == "any" ? 1 : 0;
     mo.fuse = static_cast<int>(cli.geti("fuse", 0));
+    mo.fuse_resid = cli.flag("fuse-resid") ? 1 : 0;
     if (mo.fuse != 0 && (mo.fuse < 2 || mo.fuse > GMT_MG_MAX_FUSE)) {
       if (rank == 0) std::printf("ERROR: --fuse must be 0 or 2..%d\n", GMT_MG_MAX_FUSE);
       std::fflush(stdout);
@@ -870,6 +873,8 @@ int main(int argc, char** argv) {
         if (mo.fuse)
           std::printf("fuse      = %d (fine level %d, %d of %d levels fused)\n", mr.fuse, mr.fuse_fine, mr.fuse_levels,
                       mr.levels - 1);
+        if (mo.fuse_resid)
+          std::printf("resid     = fused (%d of %d levels)\n", mr.resid_levels, mr.levels - 1);
       }
       if (cg_fixed)
         std::printf("solve     = fixed count, %s norm, check every %d %ss\n", co.norm ? "max" : "l2",
@@ -940,6 +945,7 @@ int main(int argc, char** argv) {
       j.add("solver", "multigrid").add("coarsen", mo.coarsen ? "any" : "nested").add("levels", mr.levels)
           .add("cycles", mr.iters).add("fuse", mr.fuse).add("fuse_fine", mr.fuse_fine)
           .add("fuse_levels", mr.fuse_levels).add("smoother", mo.smoother ? "rb" : "jacobi")
+          .add("fuse_resid", mr.fuse_resid != 0).add("resid_levels", mr.resid_levels).add("resid_mask", mr.resid_mask)
           .add("residual_cycles", mr.residual_iters).add("checks", mr.checks).add("converged", mr.converged != 0)
           .add("solve_ms", solve_ms).add("r0", mr.r0).add("residual_max", mr.residual_max);
     else if (cg_mode)

@@ -286,6 +286,7 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   mo.coarsen = o->coarsen;
   mo.fuse = o->fuse;
   mo.smoother = o->smoother;
+  mo.fuse_resid = o->fuse_resid;
   gmt::MgResult r;
   try {
     r = s.mg(mo);
@@ -296,13 +297,20 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   }
   *out = {r.converged, r.iters,  r.checks,    r.residual_iters, r.residual,     r.residual_max, r.r0,
           r.failed,    r.levels, r.coarse_ny, r.coarse_nx,      r.coarse_iters, r.coarse_rho,
-          r.fuse,      r.fuse_fine, r.fuse_levels, r.smoother};
+          r.fuse,      r.fuse_fine, r.fuse_levels, r.smoother,    r.fuse_resid,   r.resid_levels, r.resid_mask};
   return 0;
 }
 int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
                               int coarsen, int* out, int max) {
   if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || coarsen < 0 || coarsen > 1 || !out) return -1;
   const auto d = gmt::mg_fuse_depths(ny, nx, py, px, fuse, ghost, max_levels, coarsen);
+  for (int i = 0; i < static_cast<int>(d.size()) && i < max; ++i) out[i] = d[i];
+  return static_cast<int>(d.size());
+}
+int gmt_engine_mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen,
+                               int* out, int max) {
+  if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || coarsen < 0 || coarsen > 1 || !out) return -1;
+  const auto d = gmt::mg_resid_levels(ny, nx, py, px, ghost, max_levels, coarsen);
   for (int i = 0; i < static_cast<int>(d.size()) && i < max; ++i) out[i] = d[i];
   return static_cast<int>(d.size());
 }

@@ -1444,7 +1444,23 @@ int64_t mg_min_share(const std::vector<int64_t>& b) {
   for (size_t k = 1; k + 1 < b.size(); ++k) m = std::min(m, b[k + 1] - b[k]);
   return m;
 }
+// a restricting level runs gmt_mg_resid_restrict (min shares as above)
+bool mg_resid_level(bool tab, int64_t min_ny, int64_t min_nx, bool fine, int ranks, int ghost) {
+  if (tab) return false;
+  if (ranks == 1) return true;
+  if ((min_ny > 0 && min_ny < 2) || (min_nx > 0 && min_nx < 2)) return false;
+  return !fine || ghost >= 2;
+}
 }  // namespace
+
+std::vector<int> mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen) {
+  const auto shapes = mg_hierarchy(ny, nx, py, px, max_levels, coarsen);
+  std::vector<int> out;
+  for (size_t l = 0; l + 1 < shapes.size(); ++l)
+    out.push_back(mg_resid_level(shapes[l].ny % 2 == 0 || shapes[l].nx % 2 == 0, mg_min_share(shapes[l].by),
+                                 mg_min_share(shapes[l].bx), l == 0, py * px, ghost));
+  return out;
+}
 
 std::vector<int> mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
                                 int coarsen) {
@@ -1510,7 +1526,7 @@ void JacobiSolver::mg_setup() {
       L.dld = std::max(L.ld, round_up(L.xo + L.nx + kMgTapHalo, 64));
       elems = static_cast<size_t>(L.dld) * (L.dyo + L.ny + kMgTapHalo);
     }
-    L.d = zeroed(elems);
+    L.delems = elems;  // d itself when a call first runs the level's residual unfused (mg_fuse_setup)
   }
   if (!mg_ws_.data())
     mg_ws_ = Buffer<double>(static_cast<size_t>(gmt_cg_workspace(nx_, ny_)) + 2, GMT_SPACE_DEVICE);
@@ -1519,8 +1535,6 @@ void JacobiSolver::mg_setup() {
     MgLevel& L = mg[l];
     if (l > 0)
       for (int b = 0; b < 2; ++b) L.hu[b] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true);
-    if (!L.d.data()) continue;
-    L.hd = ring_halo(L.d.data(), L.xo, L.dyo, L.nx, L.ny, L.dld, true, L.tab ? kMgTapHalo : 1);
     if (!L.tab) continue;
     // the tables of this rank's share, checked on the host before they reach the device
     const MgLevel& C = mg[l + 1];
@@ -1545,32 +1559,45 @@ void JacobiSolver::mg_ring(int l) {
 }
 
 // The depth of every smoothing level of this call (mg_fuse_depths' rule on the
-// shares mg_setup kept) and, on first use, the wide halo plans it needs: of
-// either buffer at the level's depth, of the source one cell narrower.  Level
+// shares mg_setup kept), whether a restricting level fuses its residual into
+// the restriction (mg_resid_levels' rule) and, on first use, what the level
+// needs: the wide halo plans of either buffer (at the level's depth, 2-wide
+// for the fused transfer) and of the source (one cell narrower), or the
+// residual field d and its ring's plan where the transfer runs unfused.  Level
 // 0's source ring is exchanged here, once per source.
 void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
   std::vector<MgLevel>& mg = mg_[mgh_];
   for (int l = 0; l < static_cast<int>(mg.size()); ++l) {
     MgLevel& L = mg[l];
     L.depth = l + 1 < levels ? mg_fuse_depth(o.fuse, L.min_ny, L.min_nx, l == 0, t_.size(), g_) : 1;
-    if (L.depth < 2 || t_.size() == 1) continue;
-    const int d = L.depth;
-    for (int b = 0; b < 2; ++b) {
-      if (L.hk[b][d] && L.hk_field[b] == L.up[b]) continue;
-      L.hk[b][d] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true, d);
-      L.hk_field[b] = L.up[b];
+    L.resid = l + 1 < levels && o.fuse_resid != 0 &&
+              mg_resid_level(L.tab, L.min_ny, L.min_nx, l == 0, t_.size(), g_);
+    L.sw = std::max(L.depth >= 2 ? L.depth - 1 : 0, L.resid ? 1 : 0);
+    if (l + 1 < levels && !L.resid && !L.d.data()) {
+      L.d = Buffer<double>(L.delems, GMT_SPACE_DEVICE);
+      GMT_CHECK("memset", gmt_rt_memset_async(L.d.data(), 0, L.d.bytes(), s_));
+      GMT_CHECK("mg set-up sync", gmt_rt_stream_synchronize(s_));
+      L.hd = ring_halo(L.d.data(), L.xo, L.dyo, L.nx, L.ny, L.dld, true, L.tab ? kMgTapHalo : 1);
     }
-    if (L.sp && !L.hs[d - 1])
-      L.hs[d - 1] = ring_halo(const_cast<double*>(L.sp), L.xo, L.yo, L.nx, L.ny, L.ld, true, d - 1);
+    if (t_.size() == 1) continue;
+    for (int b = 0; b < 2; ++b) {
+      if (L.hk_field[b] != L.up[b])  // plans of a buffer that is gone
+        for (auto& h : L.hk[b]) h.reset();
+      L.hk_field[b] = L.up[b];
+      for (const int w : {L.depth, L.resid ? 2 : 1})
+        if (w >= 2 && !L.hk[b][w]) L.hk[b][w] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true, w);
+    }
+    if (L.sw > 0 && L.sp && !L.hs[L.sw])
+      L.hs[L.sw] = ring_halo(const_cast<double*>(L.sp), L.xo, L.yo, L.nx, L.ny, L.ld, true, L.sw);
   }
   MgLevel& F = mg[0];
-  if (F.depth >= 2 && F.sp && t_.size() > 1 && f_ring_ < F.depth - 1) {
-    Halo2D& h = *F.hs[F.depth - 1];
+  if (F.sw > 0 && F.sp && t_.size() > 1 && f_ring_ < F.sw) {
+    Halo2D& h = *F.hs[F.sw];
     if (h.active()) {
       h.start(s_);
       h.finish(s_);
     }
-    f_ring_ = F.depth - 1;
+    f_ring_ = F.sw;
   }
 }
 
@@ -1653,25 +1680,43 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
   MgLevel& C = mg_[mgh_][l + 1];
   const int px = L.ox % 2 == 0 ? 1 : 0, py = L.oy % 2 == 0 ? 1 : 0;
   smooth(o.nu1);
-  mg_ring(l);
-  // d in its own layout: row yo of u is row dyo of d
-  double* dv = L.d.data() + (L.dyo - L.yo) * L.dld;
-  GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, dv, L.dld,
-                                        mg_ws_.data(), mg_ws_.data() + 2, s_));
-  if (L.hd->active()) {
-    L.hd->start(s_);
-    L.hd->finish(s_);
+  if (L.resid) {
+    // the residual on the ring of d comes from the neighbours' cells two deep; a rank without neighbours
+    // reads its fixed ring only
+    const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
+                     (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+    if (mask != 0) {
+      Halo2D& h = *L.hk[L.cur][2];
+      if (h.active()) {
+        h.start(s_);
+        h.finish(s_);
+      }
+      L.ring = true;
+    }
+    GMT_CHECK("mg fused residual and restrict",
+              gmt_mg_resid_restrict(L.xo, L.nx, L.yo, L.ny, px, py, mask, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, kC0,
+                                    C.s.data(), C.xo, C.yo, C.ld, s_));
+  } else {
+    mg_ring(l);
+    // d in its own layout: row yo of u is row dyo of d
+    double* dv = L.d.data() + (L.dyo - L.yo) * L.dld;
+    GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, dv, L.dld,
+                                          mg_ws_.data(), mg_ws_.data() + 2, s_));
+    if (L.hd->active()) {
+      L.hd->start(s_);
+      L.hd->finish(s_);
+    }
+    if (L.tab)
+      GMT_CHECK("mg restrict", gmt_mg_restrict_tab(L.plan.get(), L.xo, L.dyo, L.d.data(), L.dld, C.s.data(), C.xo,
+                                                   C.yo, C.ld, s_));
+    else
+      GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
+                                               C.yo, C.ld, s_));
   }
-  if (L.tab)
-    GMT_CHECK("mg restrict", gmt_mg_restrict_tab(L.plan.get(), L.xo, L.dyo, L.d.data(), L.dld, C.s.data(), C.xo, C.yo,
-                                                 C.ld, s_));
-  else
-    GMT_CHECK("mg restrict", gmt_mg_restrict(L.xo, L.nx, L.yo, L.ny, px, py, L.d.data(), L.ld, kC0, C.s.data(), C.xo,
-                                             C.yo, C.ld, s_));
-  // a fused coarser level reads the ring of its source too
-  if (C.depth >= 2 && l + 1 < levels - 1 && C.hs[C.depth - 1] && C.hs[C.depth - 1]->active()) {
-    C.hs[C.depth - 1]->start(s_);
-    C.hs[C.depth - 1]->finish(s_);
+  // a coarser level with fused smoothing or a fused transfer reads the ring of its source too
+  if (C.sw > 0 && C.hs[C.sw] && C.hs[C.sw]->active()) {
+    C.hs[C.sw]->start(s_);
+    C.hs[C.sw]->finish(s_);
   }
   // u = 0 on the coarser level, ring included: current on every rank
   GMT_CHECK("memset", gmt_rt_memset_async(C.up[0], 0, C.u[0].bytes(), s_));
@@ -1700,9 +1745,9 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
                     o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1) &&
                     (o.fuse == 0 || (o.fuse >= 2 && o.fuse <= GMT_MG_MAX_FUSE)) &&
-                    (o.smoother == 0 || o.smoother == 1),
+                    (o.smoother == 0 || o.smoother == 1) && (o.fuse_resid == 0 || o.fuse_resid == 1),
                 ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0, "
-                "coarsen 0 or 1, fuse 0 or 2..4, smoother 0 or 1");
+                "coarsen 0 or 1, fuse 0 or 2..4, smoother 0 or 1, fuse_resid 0 or 1");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
   const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels, o.coarsen);
@@ -1714,7 +1759,7 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
              : o.coarsen == 0 ? "a rank of the process grid would own no coarse point"
                               : "the extents are too small or a rank of the process grid would own no coarse point"));
   mgc_ = o.coarsen;
-  mgh_ = o.coarsen + (o.fuse > 0 ? 2 : 0);
+  mgh_ = o.coarsen + (o.fuse > 0 || o.fuse_resid ? 2 : 0);
   mg_setup();
   const int levels = static_cast<int>(table.size());
   MgResult res;
@@ -1731,6 +1776,9 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   res.smoother = o.smoother;
   res.fuse_fine = F.depth;
   for (int l = 0; l + 1 < levels; ++l) res.fuse_levels += mg_[mgh_][l].depth >= 2;
+  res.fuse_resid = o.fuse_resid;
+  for (int l = 0; l + 1 < levels; ++l)
+    if (mg_[mgh_][l].resid) ++res.resid_levels, res.resid_mask |= 1 << l;
   F.cur = parity_;
   F.ring = fresh_[parity_];
   run_checks(loop, res,

@@ -572,6 +572,56 @@ int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int 
   return 0;
 }
 
+// the residual and its full weighting: the definition, through a zeroed scratch field d
+int gmt_mg_resid_restrict_geom(int64_t* wave_cols, int64_t* block_cols) {
+  return gmt_mg_smooth_k_geom(2, wave_cols, block_cols);
+}
+
+int gmt_mg_resid_restrict_path(int64_t, int64_t, int64_t, int64_t, int, int, int, const double*, int64_t,
+                               const double*, int64_t, const double*, int64_t, int64_t, int64_t, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
+                          const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1, double cs,
+                          double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void*) {
+  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0) return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
+  const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
+             hn = halo_mask & GMT_MG_HALO_N;
+  const int64_t gw = hw ? 2 : 1, ge = he ? 2 : 1, gs = hs ? 2 : 1, gn = hn ? 2 : 1;
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (!u || !sc || x0 < gw || y0 < gs || cx0 < 0 || cy0 < 0 || ld < x0 + nx + ge || ldc < cx0 + mx ||
+      (f && ldf < x0 + nx + (ge - 1)))
+    return 1;
+  if (mx == 0 || my == 0) return 0;
+  {  // the read sets of u and f against sc's cells, as address ranges
+    const double* oa = sc + cy0 * ldc + cx0;
+    const double* oe = sc + (cy0 + my - 1) * ldc + (cx0 + mx);
+    const double* ua = u + (y0 - gs) * ld + (x0 - gw);
+    const double* ue = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
+    if (ua < oe && oa < ue) return 1;
+    if (f) {
+      const double* fa = f + (y0 - (gs - 1)) * ldf + (x0 - (gw - 1));
+      const double* fe = f + (y0 + ny + gn - 2) * ldf + (x0 + nx + ge - 1);
+      if (fa < oe && oa < fe) return 1;
+    }
+  }
+  // d: the region and its ring, cell (0, 0) at (x0 - 1, y0 - 1); the residual on the grown box
+  const int64_t wx = nx + 2, wy = ny + 2;
+  std::vector<double> d(static_cast<size_t>(wx * wy), 0.0);
+  for (int64_t y = y0 - (hs ? 1 : 0); y < y0 + ny + (hn ? 1 : 0); ++y)
+    for (int64_t x = x0 - (hw ? 1 : 0); x < x0 + nx + (he ? 1 : 0); ++x) {
+      const double* c = u + y * ld + x;  // gmt_cg_apply mode 1's cell
+      double o = c0 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
+      if (f) o = o + c1 * f[y * ldf + x];
+      d[(y - y0 + 1) * wx + (x - x0 + 1)] = o - c[0];
+    }
+  return gmt_mg_restrict(1, nx, 1, ny, px, py, d.data(), wx, cs, sc, cx0, cy0, ldc, nullptr);
+}
+
 int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* e, int64_t cx0,
                        int64_t cy0, int64_t lde, double* u, int64_t ld, void*) {
   if (nx < 0 || ny < 0) return 1;

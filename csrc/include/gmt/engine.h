@@ -138,6 +138,7 @@ typedef struct gmt_engine_mg_opts {
   int coarsen;      /* 0 nested (nx + 1 and ny + 1 even on every level), 1 any lattice size (MgOpts::coarsen) */
   int fuse;         /* 0, or 2..4: sweeps of a smoothing run per memory pass (MgOpts::fuse) */
   int smoother;     /* 0 damped Jacobi, 1 red-black Gauss-Seidel (MgOpts::smoother); omega is taken as given */
+  int fuse_resid;   /* 1: residual and restriction in one pass where a level allows it (MgOpts::fuse_resid) */
 } gmt_engine_mg_opts;
 typedef struct gmt_engine_mg_result {
   int converged, iters, checks, residual_iters;
@@ -149,6 +150,8 @@ typedef struct gmt_engine_mg_result {
   double coarse_rho;
   int fuse, fuse_fine, fuse_levels; /* as requested; the depth of level 0; levels with a depth >= 2 */
   int smoother;                     /* as requested */
+  int fuse_resid, resid_levels;     /* as requested; the levels whose residual and restriction ran fused */
+  int resid_mask;                   /* bit l: level l is one of them */
 } gmt_engine_mg_result;
 /* 0; 1 on invalid options, 2 on an engine with a periodic axis, 3 when the
  * problem has no coarse level: nx + 1 or ny + 1 odd, 4 when a rank of the
@@ -163,6 +166,10 @@ int gmt_engine_mg_levels(int64_t ny, int64_t nx, int py, int px, int max_levels,
 /* the same under gmt_engine_mg_opts.coarsen (0: the table above); -1 on a bad argument */
 int gmt_engine_mg_levels2(int64_t ny, int64_t nx, int py, int px, int max_levels, int coarsen, int64_t* out,
                           int max);
+/* 1 or 0 per restricting level: its residual and restriction fuse under gmt_engine_mg_opts.fuse_resid on an
+ * engine of ghost depth `ghost` (gmt::mg_resid_levels) into out[max]; returns their number, -1 on a bad argument */
+int gmt_engine_mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen,
+                               int* out, int max);
 /* the depth of every smoothing level under gmt_engine_mg_opts.fuse on an engine of ghost depth `ghost`
  * (gmt::mg_fuse_depths) into out[max]; returns their number, -1 on a bad argument */
 int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,

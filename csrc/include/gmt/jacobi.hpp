@@ -235,6 +235,7 @@ struct MgOpts {
   int coarsen = 0;               // 0 nested; 1 any: every lattice size (both above)
   int fuse = 0;                  // 0, or 2..GMT_MG_MAX_FUSE: sweeps of a smoothing run per memory pass (below)
   int smoother = 0;              // 0 damped Jacobi; 1 red-black Gauss-Seidel (below)
+  int fuse_resid = 0;            // 1: residual and restriction in one memory pass where a level allows it (below)
 };
 struct MgResult : CheckResult {
   int levels = 0;                          // levels used, the fine one included
@@ -245,6 +246,8 @@ struct MgResult : CheckResult {
   int fuse_fine = 1;                       // the depth of level 0 (1: it smooths sweep by sweep)
   int fuse_levels = 0;                     // smoothing levels with a depth >= 2
   int smoother = 0;                        // MgOpts::smoother as requested
+  int fuse_resid = 0;                      // MgOpts::fuse_resid as requested
+  int resid_levels = 0, resid_mask = 0;    // the levels that ran gmt_mg_resid_restrict, and bit l for level l
 };
 // MgOpts::fuse > 0 runs the sweeps of a smoothing run through gmt_mg_smooth_k,
 // up to `fuse` of them per memory pass, for the same bits.  Every smoothing
@@ -271,6 +274,21 @@ struct MgResult : CheckResult {
 // comes from the rank's global offset on the level and the half-sweeps the run
 // has done, so the field does not depend on the process grid.  Depths, halo
 // plans, source rings, residual, transfers and the coarsest level are the same.
+// MgOpts::fuse_resid = 1 replaces, on a restricting level, the ring exchange,
+// the residual (gmt_cg_apply mode 1 into the field d), the exchange of d's ring
+// and the restriction by one 2-wide exchange of the current buffer with
+// corners and one gmt_mg_resid_restrict whose halo sides are the sides with a
+// neighbour, for the same bits.  A level fuses iff its transfer is not
+// table-driven, there is one rank or every rank owns at least 2 cells of the
+// level on each axis the process grid shares, and, on level 0 of several
+// ranks, the engine's ghost depth is at least 2; the other levels run the
+// launches above.  A function of global shapes only.  Such a call uses the
+// hierarchy of fused calls whatever `fuse` is, keeps the 1-wide ring of the
+// level's source with corners current (with fused smoothing, the wider of the
+// two), and a level that fuses gets its d and d's halo plan only when a later
+// call runs it unfused.
+// 1 or 0 for each restricting level (the coarsest level has none).
+std::vector<int> mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen);
 // The depth of each smoothing level (the coarsest level has none).
 std::vector<int> mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
                                 int coarsen);
@@ -471,7 +489,7 @@ class JacobiSolver {
   std::unique_ptr<Halo2D> ring_halo(double* field, int64_t xo, int64_t yo, int64_t nx, int64_t ny, int64_t ld,
                                     bool corners, int width = 1);
   void mg_setup();          // the levels of mg() for mgh_ (first use; collective)
-  void mg_fuse_setup(int levels, const MgOpts& o);  // depths and the wide halo plans of a fused call (collective)
+  void mg_fuse_setup(int levels, const MgOpts& o);  // depths, fused transfers and what they need (collective)
   void mg_smooth_run(int l, int n, const MgOpts& o);  // n sweeps on level l, fused where its depth allows
   void mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho);
   void mg_ring(int l);      // the faces of level l's current buffer hold the neighbours' current values
@@ -547,6 +565,11 @@ class JacobiSolver {
     // of either buffer and of the source, made on first use
     int64_t min_nx = 0, min_ny = 0;
     int depth = 1;
+    // MgOpts::fuse_resid: the level runs gmt_mg_resid_restrict in this call; the width at which the ring of its
+    // source is kept current; the doubles of d, allocated when a call first needs it
+    bool resid = false;
+    int sw = 0;
+    size_t delems = 0;
     std::unique_ptr<Halo2D> hk[2][GMT_MG_MAX_FUSE + 1], hs[GMT_MG_MAX_FUSE];
     double* hk_field[2] = {nullptr, nullptr};
   };

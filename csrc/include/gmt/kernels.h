@@ -404,6 +404,49 @@ int gmt_mg_smooth_rb_path(int h, int par, int64_t x0, int64_t nx, int64_t ny, in
                           int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo,
                           int64_t* seg_rows);
 
+/* ---- The residual and its full weighting in one memory pass: the composition
+ *      of gmt_cg_apply mode 1 and gmt_mg_restrict without the field between
+ *      them.  Let D be the field gmt_cg_apply mode 1 writes,
+ *      q = c0*((W+E)+(S+N)) [+ c1*f] - u (the same order, no contraction), on
+ *      the region R = nx x ny at (x0, y0) grown by one cell on every side
+ *      whose halo_mask bit is set (W = 1, E = 2, S = 4, N = 8; corner cells
+ *      where two set sides meet), and +0.0 on every other cell of R's 1-wide
+ *      ring.  sc is then exactly gmt_mg_restrict(x0, nx, y0, ny, px, py, D, cs,
+ *      sc, cx0, cy0): the same H and cs*((H(y-1) + H(y+1)) + 2*H(y)).  So sc is
+ *      bitwise what the two calls give with the ring of d exchanged with a
+ *      neighbour (set sides) or left zero (clear sides); D is never stored.
+ *      u is read on R plus 2 cells beyond a set side and 1 beyond a clear
+ *      side, without the outermost corner cell where two set sides meet (the
+ *      cells gmt_mg_smooth_k(2, ...) reads); f on R plus 1 cell beyond set
+ *      sides only; only sc's mx x my cells are written; 8 B per fine point read
+ *      (16 with f), 2 written.
+ *      Refused (non-zero, nothing launched, the same on both backends): every
+ *      refusal of gmt_cg_apply and gmt_mg_restrict, a mask outside 0..15,
+ *      x0 < 2 or y0 < 2 with that side's bit set, a pitch shorter than the
+ *      read sets (ld >= x0 + nx + 2 with E set, else + 1; ldf >= x0 + nx + 1
+ *      with E set, else + 0), sc's cells overlapping a read set.  An empty
+ *      region launches nothing and returns 0.
+ *      The fast path (GMT_PATH_ROW_WALK: x0 and cx0 even, every pointer 16-B
+ *      aligned, every pitch even) is the two-level row walk of
+ *      gmt_mg_smooth_k(2) in its geometry: level 1 is the residual cell, +0.0
+ *      where the smoother would keep a cell; level 2 is H of the lane's coarse
+ *      column with its W or E operand through DPP; a lane keeps H of the last
+ *      two fine rows and stores one coarse cell every second row.  Everything
+ *      else takes one lane per coarse cell (GMT_PATH_SCALAR), each with its own
+ *      3 x 3 residuals.
+ *      _path: the kernel the call would launch, nothing launched; *seg_rows
+ *      (may be NULL) = the fine rows per segment of the walk, 0 otherwise;
+ *      GMT_PATH_NONE on the CPU backend and for arguments the call would
+ *      refuse.  _geom: the fine columns per wave and per workgroup of the walk
+ *      (gmt_mg_smooth_k_geom(2)). */
+int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
+                          const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1, double cs,
+                          double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void* stream);
+int gmt_mg_resid_restrict_path(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
+                               const double* u, int64_t ld, const double* f, int64_t ldf, const double* sc,
+                               int64_t cx0, int64_t cy0, int64_t ldc, int64_t* seg_rows);
+int gmt_mg_resid_restrict_geom(int64_t* wave_cols, int64_t* block_cols);
+
 /* ---- Table-driven transfers between two levels that are not nested: n fine
  *      and m coarse interior points per axis on the same interval (any m with
  *      3 or 4 fine points between the neighbours of a coarse one), linear

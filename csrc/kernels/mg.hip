@@ -27,6 +27,9 @@
 //                       (gmt/mg_tab.hpp); taps by 8-B loads out of L2.  The
 //                       restriction computes one coarse cell per lane and pairs
 //                       the lanes for the store.
+//   mg_resid_restrict_* the residual and its full weighting in one pass
+//                       (gmt_mg_resid_restrict), described where they are
+//                       defined below: 8 + 2 B/pt (16 + 2 with f).
 //   *_scalar            one cell per lane, for odd alignment or pitches.
 //
 // Every cell is evaluated without contraction, as the CPU backend's.
@@ -514,6 +517,208 @@ __global__ __launch_bounds__(kBlock) void mg_prolong_pt(int64_t x0, int64_t nx, 
   }
 }
 
+// ---- the residual and its full weighting in one pass (gmt_mg_resid_restrict) ----
+//
+//   mg_resid_restrict_walk    the two-level walk of mg_smooth_k_walk<2> in its
+//                       geometry (a wave stores the coarse cells of 124 fine
+//                       columns and loads 2 columns around them; a segment
+//                       runs 2 warm-up rows above and below its own).  Level 1
+//                       is the residual cell d, +0.0 where the smoother would
+//                       keep; level 2 is H of the lane's coarse column (fine
+//                       column c + px of its pair at c), the third operand
+//                       from the W or E lane by DPP.  The lane keeps H of the
+//                       last two fine rows; every second row it stores one
+//                       coarse cell, so a wave's store is 62 consecutive
+//                       doubles.  8 B/pt (16 with f) read, 2 B/pt written.
+//   mg_resid_restrict_scalar  one lane per coarse cell: its own 3 x 3 residuals
+//                       from the 5 x 5 cells of u without the corners.
+
+struct MgRrArgs {
+  int64_t x0, nx, y0, ny;
+  int px, py, mask;
+  const double* u;
+  int64_t ld;
+  const double* f;
+  int64_t ldf;
+  double c0, c1, cs;
+  double* sc;
+  int64_t cx0, cy0, ldc, mx, my;
+  int64_t nseg, seg_rows, nblocks;
+};
+
+template <bool HAS_F>
+__device__ __forceinline__ double mg_resid_cell(double w, double e, double n, double s, double u, double c0,
+                                                double c1, double fv) {
+#pragma clang fp contract(off)
+  double o = c0 * ((w + e) + (n + s));
+  if (HAS_F) o = o + c1 * fv;
+  return o - u;
+}
+
+template <bool HAS_F>
+__global__ __launch_bounds__(kBlock) void mg_resid_restrict_walk(const MgRrArgs a) {
+  constexpr int K = 2, SH = mg_fuse_shift(K), OC = mg_fuse_wave_cols(K);
+  constexpr int U = HAS_F ? kMgUnrollF : kMgUnrollP;
+  const double* __restrict__ u = a.u;
+  const double* __restrict__ f = a.f;
+  double* __restrict__ sc = a.sc;
+  const int64_t nx = a.nx, ny = a.ny, ld = a.ld, ldf = a.ldf;
+  const int64_t t = xcd_swizzle(blockIdx.x, a.nblocks);
+  const int64_t seg = t % a.nseg, bx = t / a.nseg;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int64_t xo = (bx * (kBlock / kWave) + wave) * OC;  // the first fine column of the wave's coarse cells
+  if (xo >= nx) return;  // wave-uniform: every lane of a working wave stays active (DPP)
+  const bool hw = a.mask & GMT_MG_HALO_W, he = a.mask & GMT_MG_HALO_E, hs = a.mask & GMT_MG_HALO_S,
+             hn = a.mask & GMT_MG_HALO_N;
+  const bool px = a.px != 0;
+  // region-relative columns, as mg_smooth_k_walk<2>: the lane's pair, u's read set [lo, hi), its whole pairs
+  const int64_t c = xo - SH + 2 * lane;
+  const int64_t lo = hw ? -K : -1, hi = nx + (he ? K : 1);
+  const int64_t lop = lo + (lo & 1), hip = (hi - 2) & ~int64_t(1);
+  const int64_t cl = mg_clamp(c, lop, hip);  // lanes outside re-read a pair inside (never used)
+  const bool west = lane == 0 || c == lop, east = lane == kWave - 1 || c == hip;
+  const bool wld = west && c - 1 >= lo && c - 1 < hi, eld = east && c + 2 >= lo && c + 2 < hi;
+  // d is computed on the region grown by one cell on halo sides and is +0.0 on the rest of the ring
+  const int64_t bl = hw ? -1 : 0, bh = nx + (he ? 1 : 0);
+  const bool dx = c >= bl && c < bh, dy = c + 1 >= bl && c + 1 < bh;
+  const bool fxo = HAS_F && dx, fyo = HAS_F && dy;  // f's read set is d's box
+  // the lane's coarse column I sits on fine column c + px
+  const int64_t I = c >> 1;
+  const bool so = c >= xo && c < xo + OC && I < a.mx;
+  const int64_t r0 = seg * a.seg_rows;
+  const int64_t r1 = r0 + a.seg_rows < ny ? r0 + a.seg_rows : ny;
+  const int64_t rlo = hs ? -K : -1, rhi = ny - 1 + (hn ? K : 1);  // u's rows
+  const int64_t dlo = hs ? -1 : 0, dhi = ny + (hn ? 1 : 0);       // d's rows [dlo, dhi), f's too
+  const double* ub = u + a.y0 * ld + a.x0;
+  const double* fb = HAS_F ? f + a.y0 * ldf + a.x0 : nullptr;
+  double* ob = sc + a.cy0 * a.ldc + a.cx0 + I;
+  d2 A{0.0, 0.0}, B{0.0, 0.0};  // the two last rows of u
+  double wB = 0.0, eB = 0.0;    // the columns beside B's pair that no lane of the wave holds
+  double Hs = 0.0, Hc = 0.0;    // H of the two last rows of d
+  for (int64_t tt = r0 - K; tt < r1 + K; tt += U) {
+    d2 cn[U], fn[U];
+    double wn[U], en[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      // rows past the read set are clamped to its last ones (loaded, not used)
+      const double* p = ub + mg_clamp(tt + j, rlo, rhi) * ld;
+      cn[j] = ld2(p + cl);
+      wn[j] = en[j] = 0.0;
+      if (wld) wn[j] = p[c - 1];
+      if (eld) en[j] = p[c + 2];
+      fn[j] = d2{0.0, 0.0};
+      if (HAS_F) {  // the row of d that is computed when row tt + j arrives
+        const double* pf = fb + mg_clamp(tt + j - 1, dlo, dhi - 1) * ldf;
+        if (fxo && fyo) {
+          fn[j] = ld2(pf + c);
+        } else {
+          if (fxo) fn[j].x = pf[c];
+          if (fyo) fn[j].y = pf[c + 1];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int64_t y = tt + j - 1;  // row tt + j of u arrives: row y of d, then H(y)
+      const bool rok = y >= dlo && y < dhi;
+      const d2 C = cn[j];
+      const double wl = dpp_from_lower(B.y), eu = dpp_from_upper(B.x);
+      const double w = west ? wB : wl, e = east ? eB : eu;
+      d2 d;
+      d.x = mg_resid_cell<HAS_F>(w, B.y, A.x, C.x, B.x, a.c0, a.c1, fn[j].x);
+      d.y = mg_resid_cell<HAS_F>(B.x, e, A.y, C.y, B.y, a.c0, a.c1, fn[j].y);
+      d.x = rok && dx ? d.x : 0.0;
+      d.y = rok && dy ? d.y : 0.0;
+      A = B;
+      B = C;
+      wB = wn[j], eB = en[j];
+      // beyond the read set's first and last pair lies the ring of a fixed side, or nothing that is needed
+      const double dwl = dpp_from_lower(d.y), deu = dpp_from_upper(d.x);
+      const double dw = west ? 0.0 : dwl, de = east ? 0.0 : deu;
+      const double h = mg_h(px ? d.x : dw, px ? d.y : d.x, px ? de : d.y);
+      const int64_t yc = y - 1;  // the coarse row centred here has all three rows of H now
+      if (((yc - a.py) & 1) == 0 && yc >= r0 && yc < r1 && so)
+        ob[((yc - a.py) >> 1) * a.ldc] = mg_full_weight(Hs, Hc, h, a.cs);
+      Hs = Hc;
+      Hc = h;
+    }
+  }
+}
+
+template <bool HAS_F>
+__global__ __launch_bounds__(kBlock) void mg_resid_restrict_scalar(const MgRrArgs a) {
+  const double* __restrict__ u = a.u;
+  const double* __restrict__ f = a.f;
+  const int64_t nx = a.nx, ny = a.ny;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= a.mx * a.my) return;
+  const int64_t I = i % a.mx, J = i / a.mx;
+  const int64_t x = a.px + 2 * I, y = a.py + 2 * J;  // region-relative centre
+  const bool hw = a.mask & GMT_MG_HALO_W, he = a.mask & GMT_MG_HALO_E, hs = a.mask & GMT_MG_HALO_S,
+             hn = a.mask & GMT_MG_HALO_N;
+  const int64_t bxl = hw ? -1 : 0, bxh = nx + (he ? 1 : 0), byl = hs ? -1 : 0, byh = ny + (hn ? 1 : 0);  // d's box
+  const double* ub = u + a.y0 * a.ld + a.x0;
+  const double* fb = HAS_F ? f + a.y0 * a.ldf + a.x0 : nullptr;
+  double v[5][5], d[3][3];  // indices are constants once unrolled: registers
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy)
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx)
+      if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) <= 3) {
+        // a cell of u is read iff a cell of d's box beside it needs it
+        const int64_t X = x + dx, Y = y + dy;
+        const bool colin = X >= bxl && X < bxh, rowin = Y >= byl && Y < byh;
+        const bool need = (colin && Y >= byl - 1 && Y <= byh) || (rowin && X >= bxl - 1 && X <= bxh);
+        v[dy + 2][dx + 2] = need ? ub[Y * a.ld + X] : 0.0;
+      }
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int64_t X = x + dx, Y = y + dy;
+      double r = 0.0;
+      if (X >= bxl && X < bxh && Y >= byl && Y < byh)
+        r = mg_resid_cell<HAS_F>(v[dy + 2][dx + 1], v[dy + 2][dx + 3], v[dy + 1][dx + 2], v[dy + 3][dx + 2],
+                                 v[dy + 2][dx + 2], a.c0, a.c1, HAS_F ? fb[Y * a.ldf + X] : 0.0);
+      d[dy + 1][dx + 1] = r;
+    }
+  const double h0 = mg_h(d[0][0], d[0][1], d[0][2]), h1 = mg_h(d[1][0], d[1][1], d[1][2]),
+               h2 = mg_h(d[2][0], d[2][1], d[2][2]);
+  a.sc[(a.cy0 + J) * a.ldc + a.cx0 + I] = mg_full_weight(h0, h1, h2, a.cs);
+}
+
+static int mg_resid_restrict_path(int64_t x0, int64_t cx0, const double* u, int64_t ld, const double* f, int64_t ldf,
+                                  const double* sc, int64_t ldc) {
+  return x0 % 2 == 0 && cx0 % 2 == 0 && walk_vec_ok(u, ld) && walk_vec_ok(sc, ldc) && (!f || walk_vec_ok(f, ldf))
+             ? GMT_PATH_ROW_WALK
+             : GMT_PATH_SCALAR;
+}
+
+// gmt_mg_resid_restrict takes these arguments (a non-empty region, the mask and the parities in range)
+static bool mg_resid_restrict_args_ok(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int mask,
+                                      const double* u, int64_t ld, const double* f, int64_t ldf, const double* sc,
+                                      int64_t cx0, int64_t cy0, int64_t ldc) {
+  const int64_t gw = mask & GMT_MG_HALO_W ? 2 : 1, ge = mask & GMT_MG_HALO_E ? 2 : 1;
+  const int64_t gs = mask & GMT_MG_HALO_S ? 2 : 1, gn = mask & GMT_MG_HALO_N ? 2 : 1;
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (!u || !sc || x0 < gw || y0 < gs || cx0 < 0 || cy0 < 0 || ld < x0 + nx + ge || ldc < cx0 + mx ||
+      (f && ldf < x0 + nx + (ge - 1)))
+    return false;
+  if (mx == 0 || my == 0) return true;
+  // the read sets of u and f against sc's cells, as address ranges
+  const double* oa = sc + cy0 * ldc + cx0;
+  const double* oe = sc + (cy0 + my - 1) * ldc + (cx0 + mx);
+  const double* ua = u + (y0 - gs) * ld + (x0 - gw);
+  const double* ue = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
+  if (ua < oe && oa < ue) return false;
+  if (f) {
+    const double* fa = f + (y0 - (gs - 1)) * ldf + (x0 - (gw - 1));
+    const double* fe = f + (y0 + ny + gn - 2) * ldf + (x0 + nx + ge - 1);
+    if (fa < oe && oa < fe) return false;
+  }
+  return true;
+}
+
 static int mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc) {
   return x0 % 2 == 0 && cx0 % 2 == 0 && walk_vec_ok(d, ldd) && walk_vec_ok(sc, ldc) ? GMT_PATH_PT : GMT_PATH_SCALAR;
 }
@@ -794,6 +999,59 @@ extern "C" int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, i
     const int64_t nb = (mx * my + kBlock - 1) / kBlock;
     if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
     mg_restrict_scalar<<<grid_1d(nb), kBlock, 0, s>>>(x0, y0, px, py, mx, my, d, ldd, cs, sc, cx0, cy0, ldc);
+  }
+  GMT_RET_LAUNCH();
+}
+
+extern "C" int gmt_mg_resid_restrict_geom(int64_t* wave_cols, int64_t* block_cols) {
+  return gmt_mg_smooth_k_geom(2, wave_cols, block_cols);
+}
+
+extern "C" int gmt_mg_resid_restrict_path(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
+                                          int halo_mask, const double* u, int64_t ld, const double* f, int64_t ldf,
+                                          const double* sc, int64_t cx0, int64_t cy0, int64_t ldc,
+                                          int64_t* seg_rows) {
+  using namespace gmt;
+  if (seg_rows) *seg_rows = 0;
+  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0 || px < 0 || px > 1 || py < 0 || py > 1)
+    return GMT_PATH_NONE;
+  if (nx > 0 && ny > 0 && !mg_resid_restrict_args_ok(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc))
+    return GMT_PATH_NONE;
+  const int path = mg_resid_restrict_path(x0, cx0, u, ld, f, ldf, sc, ldc);
+  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(2, nx, ny);
+  return path;
+}
+
+extern "C" int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
+                                     const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
+                                     double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
+  if (nx == 0 || ny == 0) return 0;
+  if (px < 0 || px > 1 || py < 0 || py > 1) return static_cast<int>(hipErrorInvalidValue);
+  if (!mg_resid_restrict_args_ok(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc))
+    return static_cast<int>(hipErrorInvalidValue);
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (mx == 0 || my == 0) return 0;  // no coarse point on the region
+  MgRrArgs a{x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, c0, c1, cs, sc, cx0, cy0, ldc, mx, my, 0, 0, 0};
+  if (mg_resid_restrict_path(x0, cx0, u, ld, f, ldf, sc, ldc) == GMT_PATH_ROW_WALK) {
+    const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(2)) * (kBlock / kWave);
+    a.seg_rows = mg_fuse_seg_rows(2, nx, ny);
+    a.nseg = (ny + a.seg_rows - 1) / a.seg_rows;
+    a.nblocks = (nx + bc - 1) / bc * a.nseg;
+    if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
+    if (f)
+      mg_resid_restrict_walk<true><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
+    else
+      mg_resid_restrict_walk<false><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
+  } else {
+    const int64_t nb = (mx * my + kBlock - 1) / kBlock;
+    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    if (f)
+      mg_resid_restrict_scalar<true><<<grid_1d(nb), kBlock, 0, s>>>(a);
+    else
+      mg_resid_restrict_scalar<false><<<grid_1d(nb), kBlock, 0, s>>>(a);
   }
   GMT_RET_LAUNCH();
 }

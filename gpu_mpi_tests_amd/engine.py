@@ -104,7 +104,7 @@ class MgOpts(ctypes.Structure):
                 ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
                 ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
                 ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int),
-                ("fuse", ctypes.c_int), ("smoother", ctypes.c_int)]
+                ("fuse", ctypes.c_int), ("smoother", ctypes.c_int), ("fuse_resid", ctypes.c_int)]
 
 
 class MgResult(ctypes.Structure):
@@ -115,7 +115,8 @@ class MgResult(ctypes.Structure):
                 ("levels", ctypes.c_int), ("coarse_ny", ctypes.c_int64), ("coarse_nx", ctypes.c_int64),
                 ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double),
                 ("fuse", ctypes.c_int), ("fuse_fine", ctypes.c_int), ("fuse_levels", ctypes.c_int),
-                ("smoother", ctypes.c_int)]
+                ("smoother", ctypes.c_int), ("fuse_resid", ctypes.c_int), ("resid_levels", ctypes.c_int),
+                ("resid_mask", ctypes.c_int)]
 
 
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
@@ -703,7 +704,8 @@ class NativeJacobi:
 
     def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
            lag: int = 1, nu: tuple = (2, 2), omega: "float | None" = None, max_levels: int = 0,
-           coarse_iters: int = 0, coarsen: str = "nested", fuse: int = 0, smoother: str = "jacobi") -> dict:
+           coarse_iters: int = 0, coarsen: str = "nested", fuse: int = 0, smoother: str = "jacobi",
+           fuse_resid: bool = False) -> dict:
         """Geometric multigrid V-cycles from the current field
         (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
         ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
@@ -742,6 +744,11 @@ class NativeJacobi:
         level 0 the engine's ghost depth: ``tsteps=1`` keeps the fine level of
         a multi-rank engine unfused while its coarse levels fuse); ``fuse_fine``
         is level 0's depth, ``fuse_levels`` the levels of depth >= 2.
+        ``fuse_resid=True`` computes the residual and its restriction in one
+        memory pass (gmt_mg_resid_restrict) behind one 2-wide exchange, for the
+        same bits, on every level :func:`mg_resid_levels` lists; the other
+        levels run the two kernels.  ``resid_levels`` lists the levels that
+        ran fused.
         Identical on every rank.  ValueError on bad options, a periodic axis,
         or a problem with no coarse level (``nx + 1`` or ``ny + 1`` odd, or a
         rank that would own no coarse point).  Collective."""
@@ -771,7 +778,8 @@ class NativeJacobi:
             raise ValueError(f"fuse must be 0 or 2..{MG_MAX_FUSE}, got {fuse!r}")
         o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
                    nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters),
-                   coarsen=COARSEN[coarsen], fuse=int(fuse), smoother=SMOOTHERS[smoother])
+                   coarsen=COARSEN[coarsen], fuse=int(fuse), smoother=SMOOTHERS[smoother],
+                   fuse_resid=int(bool(fuse_resid)))
         r = MgResult()
         rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
         if rc == 2:
@@ -786,6 +794,9 @@ class NativeJacobi:
         out = {n: getattr(r, n) for n, _ in MgResult._fields_}
         out["smoother"] = smoother
         out["omega"] = omega
+        out["fuse_resid"] = bool(r.fuse_resid)
+        out["resid_levels"] = [l for l in range(r.levels) if r.resid_mask >> l & 1]
+        del out["resid_mask"]
         return out
 
     def interior(self) -> np.ndarray:
@@ -1222,6 +1233,28 @@ def mg_fuse_depths(ny: int, nx: int, dims: tuple, fuse: int, ghost: int, max_lev
         if l == 0 and int(dims[0]) * int(dims[1]) > 1:
             d = min(d, int(ghost))
         out.append(max(d, 1))
+    return out
+
+
+def mg_resid_levels(ny: int, nx: int, dims: tuple, ghost: int, max_levels: int = 0, coarsen: str = "nested") -> list:
+    """The levels of ``mg(fuse_resid=True)`` whose residual and restriction run
+    as one gmt_mg_resid_restrict: a restricting level of :func:`mg_levels`
+    fuses iff both its extents are odd (its transfer is not table-driven),
+    there is one rank or every rank owns at least 2 cells of the level on each
+    axis of the ``dims = (py, px)`` grid with more than one rank, and, on level
+    0 of several ranks, ``ghost >= 2`` (the engine's ghost depth, its
+    ``tsteps``).  The Python model of gmt::mg_resid_levels."""
+    shares = []
+    levels = mg_levels(ny, nx, dims, max_levels, coarsen, shares)
+    ranks = int(dims[0]) * int(dims[1])
+    out = []
+    for l, ((my, mx), (by, bx)) in enumerate(zip(levels[:-1], shares)):
+        ok = my % 2 == 1 and mx % 2 == 1
+        if ok and ranks > 1:
+            ok = all(b1 - b0 >= 2 for b in (by, bx) if len(b) > 2 for b0, b1 in zip(b, b[1:]))
+            ok = ok and (l > 0 or int(ghost) >= 2)
+        if ok:
+            out.append(l)
     return out
 
 

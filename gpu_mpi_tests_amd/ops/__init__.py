@@ -10,7 +10,8 @@ its read-only residual ``jacobi5_resid``, the conjugate-gradient launches
 the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
 ``mg_prolong_add``, the fused smoother ``mg_smooth_k`` (k sweeps per memory
 pass), the red-black Gauss-Seidel smoother ``mg_smooth_rb`` (h coloured
-half-sweeps per memory pass), the table-driven transfers for levels that are not nested
+half-sweeps per memory pass), the fused residual + restriction
+``mg_resid_restrict``, the table-driven transfers for levels that are not nested
 ``mg_restrict_tab`` / ``mg_prolong_add_tab``, and ``jacobi5tb`` (K fused sweeps
 per memory pass).
 """
@@ -48,6 +49,9 @@ from .kernels import (  # noqa: F401
     mg_prolong_add_path,
     mg_prolong_add_tab,
     mg_prolong_add_tab_path,
+    mg_resid_restrict,
+    mg_resid_restrict_geom,
+    mg_resid_restrict_path,
     mg_restrict,
     mg_restrict_path,
     mg_restrict_tab,

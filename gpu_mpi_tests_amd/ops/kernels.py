@@ -720,6 +720,58 @@ def mg_restrict_path(d: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, 
                                                   sc.data_ptr(), sc.stride(0)))
 
 
+def mg_resid_restrict(u: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
+                      coarse: tuple[int, int], halo_mask: int = 0, f: torch.Tensor | None = None, c0: float = 0.25,
+                      c1: float = 1.0, cs: float = 0.25) -> torch.Tensor:
+    """The residual of ``u`` and its full weighting into ``sc`` in one memory
+    pass (gmt_mg_resid_restrict): :func:`cg_apply` mode 1 followed by
+    :func:`mg_restrict` without the field between them.  ``halo_mask`` (W = 1,
+    E = 2, S = 4, N = 8): a set bit marks a side whose 2 cells of ``u`` (1 of
+    ``f``) beyond the region are a neighbour's current cells, so the ring of the
+    residual is computed there; on a clear side it is zero and the one cell of
+    ``u`` beyond the region is the fixed ring.  Bitwise
+    :func:`reference.mg_resid_restrict`.  ``sc`` must not share storage with
+    ``u`` or ``f``.  Returns ``sc``."""
+    _check2d(u, "mg_resid_restrict.u")
+    _check2d(sc, "mg_resid_restrict.sc")
+    if f is not None:
+        _check2d(f, "mg_resid_restrict.f")
+    if _overlap(u, sc) or (f is not None and _overlap(f, sc)):
+        raise ValueError("mg_resid_restrict: sc must not share storage with u or f")
+    x0, nx, y0, ny = (int(t) for t in region)
+    (px, py), (cx0, cy0) = (int(t) for t in parity), (int(t) for t in coarse)
+    if not _is_dev(sc):
+        return ref.mg_resid_restrict(u, sc, cs, x0, nx, y0, ny, px, py, int(halo_mask), cx0, cy0, f, c0, c1)
+    _native.check(_native.lib().gmt_mg_resid_restrict(x0, nx, y0, ny, px, py, int(halo_mask), u.data_ptr(),
+                                                      u.stride(0), *_ptr_ld(f), float(c0), float(c1), float(cs),
+                                                      sc.data_ptr(), cx0, cy0, sc.stride(0), _stream(sc)),
+                  "gmt_mg_resid_restrict")
+    return sc
+
+
+def mg_resid_restrict_path(u: torch.Tensor, sc: torch.Tensor, region: tuple[int, int, int, int],
+                           parity: tuple[int, int], coarse: tuple[int, int], halo_mask: int = 0,
+                           f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`mg_resid_restrict` would launch (gmt_mg_resid_restrict_path,
+    no launch): ``(PATH_ROW_WALK or PATH_SCALAR, fine rows per segment of the walk)``."""
+    x0, nx, y0, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_mg_resid_restrict_path(x0, nx, y0, ny, int(parity[0]), int(parity[1]), int(halo_mask),
+                                                    u.data_ptr(), u.stride(0), *_ptr_ld(f), sc.data_ptr(),
+                                                    int(coarse[0]), int(coarse[1]), sc.stride(0),
+                                                    ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def mg_resid_restrict_geom() -> tuple[int, int]:
+    """``(fine columns per wave, per workgroup)`` of the fused transfer's walk (gmt_mg_resid_restrict_geom)."""
+    wc, bc = ctypes.c_int64(0), ctypes.c_int64(0)
+    _native.check(_native.lib().gmt_mg_resid_restrict_geom(ctypes.cast(ctypes.pointer(wc), ctypes.c_void_p),
+                                                           ctypes.cast(ctypes.pointer(bc), ctypes.c_void_p)),
+                  "gmt_mg_resid_restrict_geom")
+    return int(wc.value), int(bc.value)
+
+
 def mg_prolong_add(e: torch.Tensor, u: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
                    coarse: tuple[int, int]) -> torch.Tensor:
     """``u += P e`` over the fine ``region = (x0, nx, y0, ny)``, P the bilinear

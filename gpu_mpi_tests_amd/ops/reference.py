@@ -281,6 +281,26 @@ def mg_restrict(d, sc, cs: float, x0: int, nx: int, y0: int, ny: int, px: int, p
     return sc
 
 
+def mg_resid_restrict(u, sc, cs: float, x0: int, nx: int, y0: int, ny: int, px: int, py: int, halo_mask: int = 0,
+                      cx0: int = 0, cy0: int = 0, f=None, c0: float = 0.25, c1: float = 1.0):
+    """gmt_mg_resid_restrict: :func:`cg_apply` mode 1 on the region grown by one
+    cell on every side whose bit is set in ``halo_mask`` (W = 1, E = 2, S = 4,
+    N = 8), into a zeroed scratch field, then :func:`mg_restrict` of that field
+    over the region.  Works on torch tensors and NumPy arrays alike."""
+    if not 0 <= halo_mask <= 15 or nx < 0 or ny < 0 or px not in (0, 1) or py not in (0, 1):
+        raise ValueError("mg_resid_restrict: a mask outside 0..15, a negative extent or a parity outside 0..1")
+    if nx > 0 and ny > 0:
+        def t(a):
+            return a if isinstance(a, torch.Tensor) else torch.from_numpy(a)
+
+        gw, ge = int(bool(halo_mask & MG_HALO_W)), int(bool(halo_mask & MG_HALO_E))
+        gs, gn = int(bool(halo_mask & MG_HALO_S)), int(bool(halo_mask & MG_HALO_N))
+        d = torch.zeros_like(t(u))
+        cg_apply(t(u), d, x0 - gw, nx + gw + ge, y0 - gs, ny + gs + gn, 1, None if f is None else t(f), c0, c1)
+        mg_restrict(d, t(sc), cs, x0, nx, y0, ny, px, py, cx0, cy0)
+    return sc
+
+
 def mg_prolong_add(e, u, x0: int, nx: int, y0: int, ny: int, px: int, py: int, cx0: int, cy0: int):
     """gmt_mg_prolong_add: u += bilinear interpolation of the coarse field e over
     the fine region; by position: ``u + e``, ``u + 0.5*(eW + eE)``,
