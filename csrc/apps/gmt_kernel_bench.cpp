@@ -30,7 +30,10 @@
 //      without and with f, compared bitwise with h launches of h = 1 and timed
 //      beside gmt_mg_smooth_k of k = h, and the fused transfer
 //      gmt_mg_resid_restrict without and with f, compared bitwise with
-//      gmt_cg_apply mode 1 + gmt_mg_restrict and timed beside the two
+//      gmt_cg_apply mode 1 + gmt_mg_restrict and timed beside the two, and the
+//      fused interpolation gmt_mg_prolong_smooth for h = 1, 2, 4 (Jacobi and
+//      red-black) without and with f, compared bitwise with gmt_mg_prolong_add +
+//      gmt_mg_smooth_k / gmt_mg_smooth_rb and timed beside the two
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -749,6 +752,71 @@ int main(int argc, char** argv) {
         std::printf("mg %lldx%lld  %s ms / (cg_apply + mg_restrict) ms = %.4f, bytes model %s  (best of %d)\n",
                     (long long)n, (long long)n, nm, st[0].min() / st[1].min(), wf ? "18/34" : "10/26", reps);
       }
+    }
+    {
+      // the interpolation fused into the first post-smoothing pass (gmt_mg_prolong_smooth, mask 0) for h = 1, 2, 4
+      // sweeps (Jacobi) and half-sweeps (red-black), without and with f: first compared bitwise with
+      // gmt_mg_prolong_add on a copy of u followed by gmt_mg_smooth_k / gmt_mg_smooth_rb, then timed beside those
+      // two launches in the order A B B A.  The byte model per fine point: 16 + 2 against 18 + 16 (24 + 2 against
+      // 18 + 24 with f), whatever h.  The pair's prolong_add adds a field of 1e-12 a call: v stays bounded.
+      Buffer<double> w(elems, GMT_SPACE_DEVICE), x(elems, GMT_SPACE_DEVICE);
+      Buffer<double> dws(static_cast<size_t>(2 * gmt_diff_sq_workspace(n, n)) + 2, GMT_SPACE_DEVICE);
+      GMT_CHECK("memset", gmt_rt_memset_async(w.data(), 0, w.bytes(), s));
+      GMT_CHECK("memset", gmt_rt_memset_async(x.data(), 0, x.bytes(), s));
+      GMT_CHECK("fill", gmt_fill_poly(3, ldc, m + 2, 0.0, 1e-12, 0.0, 0.0, e.data(), ldc, s));
+      for (int rb = 0; rb < 2; ++rb)
+        for (int h : {1, 2, 4})
+          for (int wf = 0; wf < 2; ++wf) {
+            for (double* b : {u.data(), v.data()})
+              GMT_CHECK("fill", gmt_fill_poly(0, ld, n + 2, 0.0, 1e-5, 0.0, 1e-5, b, ld, s));
+            const double* fp = wf ? f.data() : nullptr;
+            const int64_t ldf = wf ? ld : 0;
+            const double c1 = wf ? 1.0 : 0.0, om = rb ? 1.0 : 0.8;
+            char nm[40], nmp[40];
+            std::snprintf(nm, sizeof(nm), "mg_prolong_%s%d%s", rb ? "rb" : "k", h, wf ? "_f" : "");
+            std::snprintf(nmp, sizeof(nmp), "prolong_add+%s%d%s", rb ? "rb" : "k", h, wf ? "_f" : "");
+            const std::function<void()> fused = [&] {
+              GMT_CHECK(nm, gmt_mg_prolong_smooth(h, rb, 0, xo, n, 1, n, 1, 1, 0, e.data(), xo, 1, ldc, u.data(), ld, fp,
+                                                  ldf, 0.25, c1, om, w.data(), ld, s));
+            };
+            const std::function<void()> pair = [&] {
+              GMT_CHECK(nmp, gmt_mg_prolong_add(xo, n, 1, n, 1, 1, e.data(), xo, 1, ldc, v.data(), ld, s));
+              if (rb)
+                GMT_CHECK(nmp, gmt_mg_smooth_rb(h, 0, xo, n, 1, n, 0, v.data(), ld, fp, ldf, 0.25, c1, om, x.data(), ld, s));
+              else
+                GMT_CHECK(nmp, gmt_mg_smooth_k(h, xo, n, 1, n, 0, v.data(), ld, fp, ldf, 0.25, c1, om, x.data(), ld, s));
+            };
+            int64_t segp = 0;
+            const int pp = gmt_mg_prolong_smooth_path(h, rb, 0, xo, n, 1, n, 1, 1, 0, e.data(), xo, 1, ldc, u.data(), ld,
+                                                      fp, ldf, w.data(), ld, &segp);
+            fused();
+            pair();  // v is u here: the first correction
+            GMT_CHECK("diff", gmt_diff_bits(n, n, w.data() + ld + xo, ld, x.data() + ld + xo, ld, dws.data(),
+                                            dws.data() + 2, s));
+            double dres[2] = {-1.0, -1.0};
+            GMT_CHECK("D2H", gmt_rt_memcpy_async(dres, dws.data(), sizeof(dres), s));
+            GMT_CHECK("sync", gmt_rt_stream_synchronize(s));
+            std::printf("mg %lldx%lld  %s path %d (%lld rows per segment), %s bitwise mg_prolong_add + mg_smooth_%s: %s\n",
+                        (long long)n, (long long)n, nm, pp, (long long)segp, nm, rb ? "rb" : "k",
+                        dres[1] == 0.0 ? "yes" : "NO");
+            if (dres[1] != 0.0) return 1;
+            Stats st[2];
+            const int order[4] = {0, 1, 1, 0};
+            for (int rep = 0; rep < reps; ++rep)
+              for (int o = 0; o < 4; ++o) {
+                const double ms = time_ms(s, iters, order[o] == 0 ? fused : pair);
+                st[order[o]].add(ms);
+                std::printf("mg %lldx%lld rep %d  %-18s %9.4f ms\n", (long long)n, (long long)n, rep,
+                            order[o] == 0 ? nm : nmp, ms);
+              }
+            char shape[64];
+            std::snprintf(shape, sizeof(shape), "%lldx%lld best", (long long)n, (long long)n);
+            report(nm, 0, shape, st[0].min(), (wf ? 26.0 : 18.0) * n * n);
+            report(nmp, 0, shape, st[1].min(), (wf ? 42.0 : 34.0) * n * n);
+            std::printf("mg %lldx%lld  %s ms / (mg_prolong_add + mg_smooth_%s) ms = %.4f, bytes model %s  (best of %d)\n",
+                        (long long)n, (long long)n, nm, rb ? "rb" : "k", st[0].min() / st[1].min(),
+                        wf ? "26/42" : "18/34", reps);
+          }
     }
     if (nt % 2 == 0) {
       // the general transfers on nt x nt: d with room for a 2-wide ring (interior origin (8, 2)), the same

@@ -59,7 +59,7 @@
 //                           the same number of serial Chebyshev iterations with the same rho and
 //                           compares within 1e-10 * max|u0|
 //   --mg [--nu=A,B] [--omega=W] [--levels=N] [--coarse-iters=C] [--coarsen=nested|any] [--fuse=K]
-//        [--smoother=jacobi|rb] [--fuse-resid]
+//        [--smoother=jacobi|rb] [--fuse-resid] [--fuse-prolong]
 //                           geometric multigrid V-cycles instead of sweeps (JacobiSolver::mg;
 //                           Dirichlet only, exclusive with --cg and --cheby; nx + 1 and ny + 1 even):
 //                           the options of --cg with --check-every=E cycles (default 1) and n_iter the
@@ -72,7 +72,9 @@
 //                           the same bits.  --smoother=rb smooths with red-black Gauss-Seidel
 //                           (MgOpts::smoother; W then defaults to 1.0, and K counts half-sweeps);
 //                           only with --mg.  --fuse-resid computes the residual and its restriction
-//                           in one memory pass on every level that allows it (MgOpts::fuse_resid)
+//                           in one memory pass on every level that allows it (MgOpts::fuse_resid).
+//                           --fuse-prolong interpolates inside the first post-smoothing pass on every
+//                           level that allows it (MgOpts::fuse_prolong)
 //                           for the same bits
 //   --check                 rank 0 re-runs the whole problem serially on the host
 //   --json=FILE
@@ -551,13 +553,20 @@ int main(int argc, char** argv) {
   MgOpts mo;
   MgResult mr;
   if (mg_mode) {
+    // a refused --mg option: every rank decides the same from the command line and global shapes, so they
+    // leave in order; a rank's MPI_Abort could take the launcher down before it has forwarded rank 0's message
+    auto refuse = [&] {
+      std::fflush(stdout);
+      tr.reset();
+      MPI_Finalize();
+      return 1;
+    };
     const std::string nu = cli.get("nu", "2,2");
     const bool nu_ok = std::sscanf(nu.c_str(), "%d,%d", &mo.nu1, &mo.nu2) == 2;
     const std::string smoother = cli.get("smoother", "jacobi");
     if (smoother != "jacobi" && smoother != "rb") {
       if (rank == 0) std::printf("ERROR: --smoother must be jacobi or rb\n");
-      std::fflush(stdout);
-      MPI_Abort(MPI_COMM_WORLD, 1);
+      return refuse();
     }
     mo.smoother = smoother == "rb" ? 1 : 0;
     mo.omega = std::atof(cli.get("omega", mo.smoother ? "1.0" : "0.8").c_str());
@@ -566,24 +575,22 @@ int main(int argc, char** argv) {
     const std::string coarsen = cli.get("coarsen", "nested");
     if (coarsen != "nested" && coarsen != "any") {
       if (rank == 0) std::printf("ERROR: --coarsen must be nested or any\n");
-      std::fflush(stdout);
-      MPI_Abort(MPI_COMM_WORLD, 1);
+      return refuse();
     }
     mo.coarsen = coarsen == "any" ? 1 : 0;
     mo.fuse = static_cast<int>(cli.geti("fuse", 0));
     mo.fuse_resid = cli.flag("fuse-resid") ? 1 : 0;
+    mo.fuse_prolong = cli.flag("fuse-prolong") ? 1 : 0;
     if (mo.fuse != 0 && (mo.fuse < 2 || mo.fuse > GMT_MG_MAX_FUSE)) {
       if (rank == 0) std::printf("ERROR: --fuse must be 0 or 2..%d\n", GMT_MG_MAX_FUSE);
-      std::fflush(stdout);
-      MPI_Abort(MPI_COMM_WORLD, 1);
+      return refuse();
     }
     if (!nu_ok || mo.nu1 < 0 || mo.nu2 < 0 || mo.nu1 + mo.nu2 == 0 || !(mo.omega > 0 && mo.omega <= 1) ||
         mo.max_levels < 0 || mo.max_levels == 1 || mo.coarse_iters < 0) {
       if (rank == 0)
         std::printf("ERROR: --mg needs --nu=A,B (A, B >= 0, A + B > 0), --omega in (0, 1], --levels 0 or >= 2 and "
                     "--coarse-iters >= 0\n");
-      std::fflush(stdout);
-      MPI_Abort(MPI_COMM_WORLD, 1);
+      return refuse();
     }
     if (!c.periodic && mg_level_table(c.ny_global, c.nx_global, c.py, c.px, mo.max_levels, mo.coarsen).size() < 2) {
       if (rank == 0) {
@@ -596,8 +603,7 @@ int main(int argc, char** argv) {
                       "point\n", (long long)c.ny_global, (long long)c.nx_global, c.py, c.px,
                       mo.coarsen ? "the extents are too small or " : "");
       }
-      std::fflush(stdout);
-      MPI_Abort(MPI_COMM_WORLD, 1);
+      return refuse();
     }
   }
   const bool solve_mode = !cg_mode && (cli.has("tol") || cli.has("rtol"));
@@ -875,6 +881,8 @@ int main(int argc, char** argv) {
                       mr.levels - 1);
         if (mo.fuse_resid)
           std::printf("resid     = fused (%d of %d levels)\n", mr.resid_levels, mr.levels - 1);
+        if (mo.fuse_prolong)
+          std::printf("prolong   = fused (%d of %d levels)\n", mr.prolong_levels, mr.levels - 1);
       }
       if (cg_fixed)
         std::printf("solve     = fixed count, %s norm, check every %d %ss\n", co.norm ? "max" : "l2",
@@ -941,6 +949,8 @@ int main(int argc, char** argv) {
     if (solve_mode)
       j.add("converged", sr.converged != 0).add("sweeps", sr.iters).add("residual_sweeps", sr.residual_iters)
           .add("checks", sr.checks).add("solve_ms", solve_ms).add("r0", sr.r0).add("residual_max", sr.residual_max);
+    if (mg_mode && mo.fuse_prolong)
+      j.add("fuse_prolong", true).add("prolong_levels", mr.prolong_levels).add("prolong_mask", mr.prolong_mask);
     if (mg_mode)
       j.add("solver", "multigrid").add("coarsen", mo.coarsen ? "any" : "nested").add("levels", mr.levels)
           .add("cycles", mr.iters).add("fuse", mr.fuse).add("fuse_fine", mr.fuse_fine)

@@ -287,6 +287,7 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   mo.fuse = o->fuse;
   mo.smoother = o->smoother;
   mo.fuse_resid = o->fuse_resid;
+  mo.fuse_prolong = o->fuse_prolong;
   gmt::MgResult r;
   try {
     r = s.mg(mo);
@@ -297,7 +298,8 @@ int gmt_engine_jacobi_mg(void* p, const gmt_engine_mg_opts* o, gmt_engine_mg_res
   }
   *out = {r.converged, r.iters,  r.checks,    r.residual_iters, r.residual,     r.residual_max, r.r0,
           r.failed,    r.levels, r.coarse_ny, r.coarse_nx,      r.coarse_iters, r.coarse_rho,
-          r.fuse,      r.fuse_fine, r.fuse_levels, r.smoother,    r.fuse_resid,   r.resid_levels, r.resid_mask};
+          r.fuse,      r.fuse_fine, r.fuse_levels, r.smoother,    r.fuse_resid,   r.resid_levels, r.resid_mask,
+          r.fuse_prolong, r.prolong_levels, r.prolong_mask};
   return 0;
 }
 int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,
@@ -311,6 +313,15 @@ int gmt_engine_mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost
                                int* out, int max) {
   if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || coarsen < 0 || coarsen > 1 || !out) return -1;
   const auto d = gmt::mg_resid_levels(ny, nx, py, px, ghost, max_levels, coarsen);
+  for (int i = 0; i < static_cast<int>(d.size()) && i < max; ++i) out[i] = d[i];
+  return static_cast<int>(d.size());
+}
+int gmt_engine_mg_prolong_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int fuse, int nu2, int smoother,
+                                 int max_levels, int coarsen, int* out, int max) {
+  if (ny < 1 || nx < 1 || py < 1 || px < 1 || max_levels < 0 || coarsen < 0 || coarsen > 1 || nu2 < 0 ||
+      smoother < 0 || smoother > 1 || !out)
+    return -1;
+  const auto d = gmt::mg_prolong_levels(ny, nx, py, px, ghost, fuse, nu2, smoother, max_levels, coarsen);
   for (int i = 0; i < static_cast<int>(d.size()) && i < max; ++i) out[i] = d[i];
   return static_cast<int>(d.size());
 }

@@ -1451,7 +1451,29 @@ bool mg_resid_level(bool tab, int64_t min_ny, int64_t min_nx, bool fine, int ran
   if ((min_ny > 0 && min_ny < 2) || (min_nx > 0 && min_nx < 2)) return false;
   return !fine || ghost >= 2;
 }
+// a level runs gmt_mg_prolong_smooth with c sweeps or half-sweeps (the min shares of the next coarser level)
+bool mg_prolong_level(bool tab, int nu2, int c, int64_t cmin_ny, int64_t cmin_nx, int ranks) {
+  if (nu2 < 1 || tab) return false;
+  if (ranks == 1) return true;
+  const int64_t w = c / 2 + 1;
+  return !((cmin_ny > 0 && cmin_ny < w) || (cmin_nx > 0 && cmin_nx < w));
+}
+// the sweeps or half-sweeps of the first chunk of a post-smoothing run
+int mg_prolong_chunk(int nu2, int smoother, int depth) { return std::min(smoother == 1 ? 2 * nu2 : nu2, depth); }
 }  // namespace
+
+std::vector<int> mg_prolong_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int fuse, int nu2, int smoother,
+                                   int max_levels, int coarsen) {
+  const auto shapes = mg_hierarchy(ny, nx, py, px, max_levels, coarsen);
+  std::vector<int> out;
+  for (size_t l = 0; l + 1 < shapes.size(); ++l) {
+    const int d = mg_fuse_depth(fuse, mg_min_share(shapes[l].by), mg_min_share(shapes[l].bx), l == 0, py * px, ghost);
+    out.push_back(mg_prolong_level(shapes[l].ny % 2 == 0 || shapes[l].nx % 2 == 0, nu2,
+                                   mg_prolong_chunk(nu2, smoother, d), mg_min_share(shapes[l + 1].by),
+                                   mg_min_share(shapes[l + 1].bx), py * px));
+  }
+  return out;
+}
 
 std::vector<int> mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen) {
   const auto shapes = mg_hierarchy(ny, nx, py, px, max_levels, coarsen);
@@ -1563,8 +1585,10 @@ void JacobiSolver::mg_ring(int l) {
 // the restriction (mg_resid_levels' rule) and, on first use, what the level
 // needs: the wide halo plans of either buffer (at the level's depth, 2-wide
 // for the fused transfer) and of the source (one cell narrower), or the
-// residual field d and its ring's plan where the transfer runs unfused.  Level
-// 0's source ring is exchanged here, once per source.
+// residual field d and its ring's plan where the transfer runs unfused.  A
+// level that interpolates inside its post-smoothing pass (mg_prolong_levels'
+// rule) needs the next coarser level's plans c/2 + 1 wide.  Level 0's source
+// ring is exchanged here, once per source.
 void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
   std::vector<MgLevel>& mg = mg_[mgh_];
   for (int l = 0; l < static_cast<int>(mg.size()); ++l) {
@@ -1573,6 +1597,11 @@ void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
     L.resid = l + 1 < levels && o.fuse_resid != 0 &&
               mg_resid_level(L.tab, L.min_ny, L.min_nx, l == 0, t_.size(), g_);
     L.sw = std::max(L.depth >= 2 ? L.depth - 1 : 0, L.resid ? 1 : 0);
+    L.pc = mg_prolong_chunk(o.nu2, o.smoother, L.depth);
+    L.prolong = l + 1 < levels && o.fuse_prolong != 0 &&
+                mg_prolong_level(L.tab, o.nu2, L.pc, mg[l + 1].min_ny, mg[l + 1].min_nx, t_.size());
+    // the width at which the finer level reads this one's field when it interpolates
+    const int ew = l > 0 && l < levels && mg[l - 1].prolong ? mg[l - 1].pc / 2 + 1 : 1;
     if (l + 1 < levels && !L.resid && !L.d.data()) {
       L.d = Buffer<double>(L.delems, GMT_SPACE_DEVICE);
       GMT_CHECK("memset", gmt_rt_memset_async(L.d.data(), 0, L.d.bytes(), s_));
@@ -1584,7 +1613,7 @@ void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
       if (L.hk_field[b] != L.up[b])  // plans of a buffer that is gone
         for (auto& h : L.hk[b]) h.reset();
       L.hk_field[b] = L.up[b];
-      for (const int w : {L.depth, L.resid ? 2 : 1})
+      for (const int w : {L.depth, L.resid ? 2 : 1, ew, L.prolong ? L.pc : 1})
         if (w >= 2 && !L.hk[b][w]) L.hk[b][w] = ring_halo(L.up[b], L.xo, L.yo, L.nx, L.ny, L.ld, true, w);
     }
     if (L.sw > 0 && L.sp && !L.hs[L.sw])
@@ -1604,7 +1633,7 @@ void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
 // n sweeps of the smoother on level l: chunks of min(n, depth); a chunk of two
 // or more is one depth-wide exchange with corners and one gmt_mg_smooth_k.
 // Red-black: 2n half-sweeps in the same chunks, through gmt_mg_smooth_rb.
-void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o) {
+void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o, int done) {
   MgLevel& L = mg_[mgh_][l];
   const int64_t ldf = L.sp ? L.ld : 0;
   const double c1 = L.sp ? 1.0 : 0.0;
@@ -1614,6 +1643,8 @@ void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o) {
   // cell (xo, yo) has the 1-based global indices (ox + 1, oy + 1): red, due first, iff ox + oy is even
   int par = static_cast<int>((L.ox + L.oy) & 1);
   if (rb) n *= 2;
+  n -= done;
+  par ^= done & 1;
   while (n > 0) {
     const int c = std::min(n, L.depth);
     if (rb) {
@@ -1686,7 +1717,8 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
     const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
                      (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
     if (mask != 0) {
-      Halo2D& h = *L.hk[L.cur][2];
+      // a level that interpolates inside its post-smoothing pass reads this halo again, c deep: max(2, c) wide
+      Halo2D& h = *L.hk[L.cur][L.prolong && L.pc >= 2 ? L.pc : 2];
       if (h.active()) {
         h.start(s_);
         h.finish(s_);
@@ -1723,6 +1755,41 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
   C.cur = 0;
   C.ring = true;
   mg_cycle(l + 1, levels, o, coarse_iters, coarse_rho);
+  if (L.prolong) {
+    // u + P e inside the first chunk of the post-smoothing run: the halo cells of u are corrected here as
+    // their owners would, from the coarser field c/2 + 1 beyond this rank's cells; a rank without neighbours
+    // reads its fixed rings only
+    const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
+                     (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+    const int c = L.pc, cw = c / 2 + 1;
+    if (mask != 0) {
+      Halo2D& hc = cw >= 2 ? *C.hk[C.cur][cw] : *C.hu[C.cur];  // either with corners
+      if (hc.active()) {
+        hc.start(s_);
+        hc.finish(s_);
+      }
+      C.ring = true;
+      if (c >= 2 && !L.resid) {  // the fused residual left the halo this deep already
+        Halo2D& h = *L.hk[L.cur][c];
+        if (h.active()) {
+          h.start(s_);
+          h.finish(s_);
+        }
+      }
+    }
+    // c = 1: the faces are current since the residual.  Level 0's ring plan has no corners: the kernel corrects
+    // the four corner cells of B0 from stale values, and one sweep's plus-shaped stencil never reads them
+    if (c == 1) mg_ring(l);
+    const bool rb = o.smoother == 1;
+    GMT_CHECK("mg fused prolong and smooth",
+              gmt_mg_prolong_smooth(c, rb ? 1 : 0, rb ? static_cast<int>((L.ox + L.oy) & 1) : 0, L.xo, L.nx, L.yo, L.ny,
+                                    px, py, mask, C.up[C.cur], C.xo, C.yo, C.ld, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1,
+                                    o.omega, L.up[L.cur ^ 1], L.ld, s_));
+    L.cur ^= 1;
+    L.ring = false;
+    mg_smooth_run(l, o.nu2, o, c);
+    return;
+  }
   Halo2D& hc = *C.hu[C.cur];
   if (hc.active()) {
     hc.start(s_);
@@ -1745,9 +1812,10 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   loop.validate(o.nu1 >= 0 && o.nu2 >= 0 && o.nu1 + o.nu2 > 0 && o.omega > 0.0 && o.omega <= 1.0 &&
                     o.max_levels >= 0 && o.max_levels != 1 && o.coarse_iters >= 0 && (o.coarsen == 0 || o.coarsen == 1) &&
                     (o.fuse == 0 || (o.fuse >= 2 && o.fuse <= GMT_MG_MAX_FUSE)) &&
-                    (o.smoother == 0 || o.smoother == 1) && (o.fuse_resid == 0 || o.fuse_resid == 1),
+                    (o.smoother == 0 || o.smoother == 1) && (o.fuse_resid == 0 || o.fuse_resid == 1) &&
+                    (o.fuse_prolong == 0 || o.fuse_prolong == 1),
                 ", nu1 and nu2 >= 0 with nu1 + nu2 > 0, omega in (0, 1], max_levels 0 or >= 2, coarse_iters >= 0, "
-                "coarsen 0 or 1, fuse 0 or 2..4, smoother 0 or 1, fuse_resid 0 or 1");
+                "coarsen 0 or 1, fuse 0 or 2..4, smoother 0 or 1, fuse_resid 0 or 1, fuse_prolong 0 or 1");
   if (periodic())
     throw std::invalid_argument("JacobiSolver::mg: I - J is singular on a periodic axis");
   const auto table = mg_level_table(cfg_.ny_global, cfg_.nx_global, cfg_.py, cfg_.px, o.max_levels, o.coarsen);
@@ -1759,7 +1827,7 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
              : o.coarsen == 0 ? "a rank of the process grid would own no coarse point"
                               : "the extents are too small or a rank of the process grid would own no coarse point"));
   mgc_ = o.coarsen;
-  mgh_ = o.coarsen + (o.fuse > 0 || o.fuse_resid ? 2 : 0);
+  mgh_ = o.coarsen + (o.fuse > 0 || o.fuse_resid || o.fuse_prolong ? 2 : 0);
   mg_setup();
   const int levels = static_cast<int>(table.size());
   MgResult res;
@@ -1779,6 +1847,9 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   res.fuse_resid = o.fuse_resid;
   for (int l = 0; l + 1 < levels; ++l)
     if (mg_[mgh_][l].resid) ++res.resid_levels, res.resid_mask |= 1 << l;
+  res.fuse_prolong = o.fuse_prolong;
+  for (int l = 0; l + 1 < levels; ++l)
+    if (mg_[mgh_][l].prolong) ++res.prolong_levels, res.prolong_mask |= 1 << l;
   F.cur = parity_;
   F.ring = fresh_[parity_];
   run_checks(loop, res,

@@ -480,10 +480,39 @@ int gmt_mg_smooth_k_path(int, int64_t, int64_t, int64_t, int, const double*, int
   return GMT_PATH_NONE;
 }
 
-// rb: only the cells due in half-sweep j are updated (gmt_mg_smooth_rb's colour rule)
+// gmt_mg_prolong_add's cell: u' of region-relative fine cell (i, j), e at coarse cell (cx0, cy0); the indices may
+// be negative (the halo cells of gmt_mg_prolong_smooth), both divisions are exact
+static double mg_prolong_cell(const double* e, int64_t lde, int64_t i, int64_t j, int px, int py, double u) {
+  const int64_t di = i - px, dj = j - py;
+  const bool onx = (di & 1) == 0, ony = (dj & 1) == 0;
+  // the coarse column / row the cell sits on, else the one west / south of it (-1: the ring)
+  const int64_t I = onx ? di / 2 : (di + 1) / 2 - 1;
+  const int64_t J = ony ? dj / 2 : (dj + 1) / 2 - 1;
+  const double* p = e + J * lde + I;
+  double t;
+  if (onx && ony)
+    t = p[0];
+  else if (ony)
+    t = 0.5 * (p[0] + p[1]);
+  else if (onx)
+    t = 0.5 * (p[0] + p[lde]);
+  else
+    t = 0.25 * ((p[0] + p[1]) + (p[lde] + p[lde + 1]));
+  return u + t;
+}
+
+// the coarse field of gmt_mg_prolong_smooth: e at coarse cell (cx0, cy0)
+struct HostProlong {
+  const double* e;
+  int64_t lde;
+  int px, py;
+};
+
+// rb: only the cells due in half-sweep j are updated (gmt_mg_smooth_rb's colour rule); pro: level 0 is u + P e on
+// B_0 (gmt_mg_prolong_smooth)
 static int mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
                             const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
-                            double omega, double* out, int64_t ldo) {
+                            double omega, double* out, int64_t ldo, const HostProlong* pro = nullptr) {
   if (k < 1 || k > GMT_MG_MAX_FUSE || halo_mask < 0 || halo_mask > 15) return 1;
   if (nx < 0 || ny < 0) return 1;
   if (nx == 0 || ny == 0) return 0;
@@ -504,6 +533,10 @@ static int mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int
   std::vector<double> w(static_cast<size_t>(wx * wy)), t;
   for (int64_t y = 0; y < wy; ++y)
     for (int64_t x = 0; x < wx; ++x) w[y * wx + x] = u[(y0 - gs + y) * ld + (x0 - gw + x)];
+  if (pro)  // B_0 in w's coordinates
+    for (int64_t y = gs - (hs ? k : 0); y < gs + ny + (hn ? k : 0); ++y)
+      for (int64_t x = gw - (hw ? k : 0); x < gw + nx + (he ? k : 0); ++x)
+        w[y * wx + x] = mg_prolong_cell(pro->e, pro->lde, x - gw, y - gs, pro->px, pro->py, w[y * wx + x]);
   t = w;
   for (int j = 1; j <= k; ++j) {
     // B_j in w's coordinates
@@ -631,25 +664,55 @@ int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, i
   if (!e || !u || x0 < 1 || y0 < 1 || cx0 < 1 || cy0 < 1 || lde < cx0 + mx + 1 || ld < x0 + nx) return 1;
   for (int64_t j = 0; j < ny; ++j)
     for (int64_t i = 0; i < nx; ++i) {
-      const int64_t di = i - px, dj = j - py;  // >= -1
-      const bool onx = (di & 1) == 0, ony = (dj & 1) == 0;
-      // the coarse column / row the cell sits on, else the one west / south of it (-1: the ring)
-      const int64_t I = onx ? di / 2 : (di + 1) / 2 - 1;
-      const int64_t J = ony ? dj / 2 : (dj + 1) / 2 - 1;
-      const double* p = e + (cy0 + J) * lde + cx0 + I;
       double* q = u + (y0 + j) * ld + x0 + i;
-      double t;
-      if (onx && ony)
-        t = p[0];
-      else if (ony)
-        t = 0.5 * (p[0] + p[1]);
-      else if (onx)
-        t = 0.5 * (p[0] + p[lde]);
-      else
-        t = 0.25 * ((p[0] + p[1]) + (p[lde] + p[lde + 1]));
-      *q = *q + t;
+      *q = mg_prolong_cell(e + cy0 * lde + cx0, lde, i, j, px, py, *q);
     }
   return 0;
+}
+
+// the interpolation and the sweeps after it: the definition, on a copy of u's read set
+int gmt_mg_prolong_smooth_geom(int h, int64_t* wave_cols, int64_t* block_cols) {
+  return gmt_mg_smooth_k_geom(h, wave_cols, block_cols);
+}
+
+int gmt_mg_prolong_smooth_path(int, int, int, int64_t, int64_t, int64_t, int64_t, int, int, int, const double*, int64_t,
+                               int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*, int64_t,
+                               int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = 0;
+  return GMT_PATH_NONE;
+}
+
+int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
+                          int halo_mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
+                          int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
+                          int64_t ldo, void*) {
+  if (h < 1 || h > GMT_MG_MAX_FUSE || rb < 0 || rb > 1 || par < 0 || par > 1 || px < 0 || px > 1 || py < 0 ||
+      py > 1 || halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0)
+    return 1;
+  if (nx == 0 || ny == 0) return 0;
+  if (!e || !out) return 1;
+  const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
+             hn = halo_mask & GMT_MG_HALO_N;
+  // the coarse cells that may be read: h/2 + 1 beyond the region's on a halo side, the ring on the others
+  const int64_t d = h / 2 + 1, cw = hw ? d : 1, ce = he ? d : 1, cs = hs ? d : 1, cn = hn ? d : 1;
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (cx0 < cw || cy0 < cs || lde < cx0 + mx + ce) return 1;
+  if (x0 < 1 || y0 < 1 || ldo < x0 + nx) return 1;  // before out's addresses are formed
+  {  // out[R] against the read sets of e and f, as address ranges (u's: mg_smooth_levels)
+    const double* oa = out + y0 * ldo + x0;
+    const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
+    const double* ea = e + (cy0 - cs) * lde + (cx0 - cw);
+    const double* ee = e + (cy0 + my + cn - 1) * lde + (cx0 + mx + ce);
+    if (ea < oe && oa < ee) return 1;
+    if (f) {
+      const int64_t gw = hw ? h - 1 : 0, ge = he ? h - 1 : 0, gs = hs ? h - 1 : 0, gn = hn ? h - 1 : 0;
+      const double* fa = f + (y0 - gs) * ldf + (x0 - gw);
+      const double* fe = f + (y0 + ny + gn - 1) * ldf + (x0 + nx + ge);
+      if (fa < oe && oa < fe) return 1;
+    }
+  }
+  const HostProlong pro{e + cy0 * lde + cx0, lde, px, py};
+  return mg_smooth_levels(h, rb != 0, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, &pro);
 }
 
 // the table-driven transfers: the plan is the host's tables themselves

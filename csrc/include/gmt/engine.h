@@ -139,6 +139,8 @@ typedef struct gmt_engine_mg_opts {
   int fuse;         /* 0, or 2..4: sweeps of a smoothing run per memory pass (MgOpts::fuse) */
   int smoother;     /* 0 damped Jacobi, 1 red-black Gauss-Seidel (MgOpts::smoother); omega is taken as given */
   int fuse_resid;   /* 1: residual and restriction in one pass where a level allows it (MgOpts::fuse_resid) */
+  int fuse_prolong; /* 1: the interpolation inside the first post-smoothing pass where a level allows it
+                     * (MgOpts::fuse_prolong) */
 } gmt_engine_mg_opts;
 typedef struct gmt_engine_mg_result {
   int converged, iters, checks, residual_iters;
@@ -152,6 +154,8 @@ typedef struct gmt_engine_mg_result {
   int smoother;                     /* as requested */
   int fuse_resid, resid_levels;     /* as requested; the levels whose residual and restriction ran fused */
   int resid_mask;                   /* bit l: level l is one of them */
+  int fuse_prolong, prolong_levels; /* as requested; the levels whose interpolation ran inside the smoothing pass */
+  int prolong_mask;                 /* bit l: level l is one of them */
 } gmt_engine_mg_result;
 /* 0; 1 on invalid options, 2 on an engine with a periodic axis, 3 when the
  * problem has no coarse level: nx + 1 or ny + 1 odd, 4 when a rank of the
@@ -170,6 +174,11 @@ int gmt_engine_mg_levels2(int64_t ny, int64_t nx, int py, int px, int max_levels
  * engine of ghost depth `ghost` (gmt::mg_resid_levels) into out[max]; returns their number, -1 on a bad argument */
 int gmt_engine_mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen,
                                int* out, int max);
+/* 1 or 0 per level that interpolates: it runs gmt_mg_prolong_smooth under gmt_engine_mg_opts.fuse_prolong with
+ * these fuse, nu2 and smoother on an engine of ghost depth `ghost` (gmt::mg_prolong_levels) into out[max]; returns
+ * their number, -1 on a bad argument */
+int gmt_engine_mg_prolong_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int fuse, int nu2, int smoother,
+                                 int max_levels, int coarsen, int* out, int max);
 /* the depth of every smoothing level under gmt_engine_mg_opts.fuse on an engine of ghost depth `ghost`
  * (gmt::mg_fuse_depths) into out[max]; returns their number, -1 on a bad argument */
 int gmt_engine_mg_fuse_depths(int64_t ny, int64_t nx, int py, int px, int fuse, int ghost, int max_levels,

@@ -236,6 +236,7 @@ struct MgOpts {
   int fuse = 0;                  // 0, or 2..GMT_MG_MAX_FUSE: sweeps of a smoothing run per memory pass (below)
   int smoother = 0;              // 0 damped Jacobi; 1 red-black Gauss-Seidel (below)
   int fuse_resid = 0;            // 1: residual and restriction in one memory pass where a level allows it (below)
+  int fuse_prolong = 0;          // 1: the interpolation inside the first post-smoothing pass where a level allows it
 };
 struct MgResult : CheckResult {
   int levels = 0;                          // levels used, the fine one included
@@ -248,6 +249,8 @@ struct MgResult : CheckResult {
   int smoother = 0;                        // MgOpts::smoother as requested
   int fuse_resid = 0;                      // MgOpts::fuse_resid as requested
   int resid_levels = 0, resid_mask = 0;    // the levels that ran gmt_mg_resid_restrict, and bit l for level l
+  int fuse_prolong = 0;                    // MgOpts::fuse_prolong as requested
+  int prolong_levels = 0, prolong_mask = 0;  // the levels that ran gmt_mg_prolong_smooth, and bit l for level l
 };
 // MgOpts::fuse > 0 runs the sweeps of a smoothing run through gmt_mg_smooth_k,
 // up to `fuse` of them per memory pass, for the same bits.  Every smoothing
@@ -287,6 +290,24 @@ struct MgResult : CheckResult {
 // level's source with corners current (with fused smoothing, the wider of the
 // two), and a level that fuses gets its d and d's halo plan only when a later
 // call runs it unfused.
+// MgOpts::fuse_prolong = 1 replaces, on a level, gmt_mg_prolong_add and the
+// first chunk of the post-smoothing run by one gmt_mg_prolong_smooth, for the
+// same bits.  With n2 = nu2 sweeps (2 nu2 half-sweeps for red-black) and
+// c = min(n2, d_l), level l fuses iff nu2 >= 1, its transfer is not
+// table-driven, and there is one rank or every rank owns at least c/2 + 1
+// cells of level l + 1 on each axis the process grid shares.  A function of
+// global shapes only.  After the coarser level returns, its field is exchanged
+// c/2 + 1 wide with corners (1 wide today); the c-deep halo of u must hold the
+// neighbours' values before the correction, and u has not changed since the
+// residual: a level that fuses its residual too widens that exchange to
+// max(2, c), c = 1 needs nothing more than the ring the residual left current,
+// and otherwise one c-wide exchange with corners runs before the launch.
+// The launch computes the c sweeps or half-sweeps with par as the run would;
+// the other n2 - c go through the run's chunks unchanged.  Such a call uses
+// the hierarchy of fused calls whatever `fuse` is.
+// 1 or 0 for each level that interpolates (the coarsest level has none).
+std::vector<int> mg_prolong_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int fuse, int nu2, int smoother,
+                                   int max_levels, int coarsen);
 // 1 or 0 for each restricting level (the coarsest level has none).
 std::vector<int> mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int ghost, int max_levels, int coarsen);
 // The depth of each smoothing level (the coarsest level has none).
@@ -490,7 +511,8 @@ class JacobiSolver {
                                     bool corners, int width = 1);
   void mg_setup();          // the levels of mg() for mgh_ (first use; collective)
   void mg_fuse_setup(int levels, const MgOpts& o);  // depths, fused transfers and what they need (collective)
-  void mg_smooth_run(int l, int n, const MgOpts& o);  // n sweeps on level l, fused where its depth allows
+  // n sweeps on level l, fused where its depth allows; the first `done` sweeps (red-black: half-sweeps) have run
+  void mg_smooth_run(int l, int n, const MgOpts& o, int done = 0);
   void mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters, double coarse_rho);
   void mg_ring(int l);      // the faces of level l's current buffer hold the neighbours' current values
   void maybe_corrupt(int parity);  // GMT_CORRUPT_PASS fault injection
@@ -569,6 +591,9 @@ class JacobiSolver {
     // source is kept current; the doubles of d, allocated when a call first needs it
     bool resid = false;
     int sw = 0;
+    // MgOpts::fuse_prolong: the level runs gmt_mg_prolong_smooth in this call, with pc sweeps or half-sweeps
+    bool prolong = false;
+    int pc = 0;
     size_t delems = 0;
     std::unique_ptr<Halo2D> hk[2][GMT_MG_MAX_FUSE + 1], hs[GMT_MG_MAX_FUSE];
     double* hk_field[2] = {nullptr, nullptr};

@@ -447,6 +447,50 @@ int gmt_mg_resid_restrict_path(int64_t x0, int64_t nx, int64_t y0, int64_t ny, i
                                int64_t cx0, int64_t cy0, int64_t ldc, int64_t* seg_rows);
 int gmt_mg_resid_restrict_geom(int64_t* wave_cols, int64_t* block_cols);
 
+/* ---- The interpolation and the first h sweeps (rb = 0) or coloured
+ *      half-sweeps (rb = 1) after it in one memory pass: the composition of
+ *      gmt_mg_prolong_add and gmt_mg_smooth_k / gmt_mg_smooth_rb without the
+ *      corrected field between them.  Let B0 be R = nx x ny at (x0, y0) grown
+ *      by h cells on every side whose halo_mask bit is set and by nothing on
+ *      the others: the cells gmt_mg_smooth_k(h) treats as current.  U' is u
+ *      with gmt_mg_prolong_add's cell rule applied to every cell of B0, with
+ *      the same px, py, cx0, cy0 and the same operation order; a halo cell has
+ *      a negative region-relative index i and its coarse column follows from
+ *      i - px as for any other cell.  out[R] = gmt_mg_smooth_k(h, ...)(U') for
+ *      rb = 0 and gmt_mg_smooth_rb(h, par, ...)(U') for rb = 1.  The cells of
+ *      u's read set outside B0 (the fixed ring) enter as they are, not even
+ *      + 0.0 is added to them.  u, e and f are read only.
+ *      u and f are read on the sets of gmt_mg_smooth_k(h); e on the coarse
+ *      cells the rule names for B0, which lie within h/2 + 1 cells of the
+ *      region's mx x my beyond a halo side and within 1 beyond a ring side.
+ *      The fast path clamps its coarse loads to that box, so e must have every
+ *      row of it: cy0 + my + h/2 + 1 rows with N set (else + 1).  Only the
+ *      pitch can be checked from the arguments; the rows are the caller's.
+ *      Refused (non-zero, nothing launched, the same on both backends): the
+ *      refusals of gmt_mg_smooth_k / gmt_mg_smooth_rb and gmt_mg_prolong_add,
+ *      rb outside 0..1, cx0 or cy0 smaller than h/2 + 1 on a halo side,
+ *      lde < cx0 + mx + h/2 + 1 with E set (else + 1), out[R] overlapping the
+ *      read set of u, e or f.  An empty region launches nothing and returns 0.
+ *      The fast path (the alignment rule of gmt_mg_smooth for u, f and out) is
+ *      the row walk of gmt_mg_smooth_k(h) / gmt_mg_smooth_rb(h) in its
+ *      geometry: the row of u that arrives becomes U' before it enters level
+ *      1.  A lane loads the coarse cell of its pair's coarse column, 8 B, once
+ *      per coarse row and has its neighbour's through DPP; a fine row between
+ *      two coarse rows uses the sums of both.  16 + 2 B per fine point (24 + 2
+ *      with f) whatever h.  Other arguments take one lane per output cell
+ *      (GMT_PATH_SCALAR), which corrects the cells of its cone as it loads
+ *      them.  _path and _geom: as gmt_mg_smooth_k_path and
+ *      gmt_mg_smooth_k_geom(h). */
+int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
+                          int halo_mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
+                          int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
+                          int64_t ldo, void* stream);
+int gmt_mg_prolong_smooth_path(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
+                               int halo_mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
+                               int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo,
+                               int64_t* seg_rows);
+int gmt_mg_prolong_smooth_geom(int h, int64_t* wave_cols, int64_t* block_cols);
+
 /* ---- Table-driven transfers between two levels that are not nested: n fine
  *      and m coarse interior points per axis on the same interval (any m with
  *      3 or 4 fine points between the neighbours of a coarse one), linear

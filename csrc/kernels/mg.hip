@@ -30,11 +30,16 @@
 //   mg_resid_restrict_* the residual and its full weighting in one pass
 //                       (gmt_mg_resid_restrict), described where they are
 //                       defined below: 8 + 2 B/pt (16 + 2 with f).
+//   mg_smooth_k_* <PR>  the interpolation inside the fused smoother
+//                       (gmt_mg_prolong_smooth): the same two kernels with a
+//                       level-0 transform u + P e, described at MgProWalk
+//                       below: 16 + 2 B/pt (24 + 2 with f).
 //   *_scalar            one cell per lane, for odd alignment or pitches.
 //
 // Every cell is evaluated without contraction, as the CPU backend's.
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -185,10 +190,100 @@ struct MgFuseArgs {
   int par;  // red-black only: the colour phase of cell (x0, y0)
 };
 
+// gmt_mg_prolong_smooth: the coarse field behind the level-0 transform u + P e
+struct MgProArgs : MgFuseArgs {
+  const double* e;  // at coarse cell (0, 0) of the region
+  int64_t lde;
+  int px, py;
+  int64_t ilo, ihi, jlo, jhi;  // the coarse columns and rows that may be read, region-relative, inclusive
+};
+template <bool PR>
+using MgWalkArgs = std::conditional_t<PR, MgProArgs, MgFuseArgs>;
+
 __device__ __forceinline__ int64_t mg_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-template <int K, bool HAS_F, bool RB = false>
-__global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
+// The level-0 transform of gmt_mg_prolong_smooth in the walk.  A lane loads coarse cell I = c >> 1 of a coarse
+// row (8 B per lane, coalesced) and takes cells I - 1 and I + 1 from its neighbours through DPP; the first and
+// last lane of the read set load theirs.  A new coarse row arrives with every second fine row: a fine row on a
+// coarse row J uses q(J), the row between J and J + 1 uses q(J) + q(J + 1), in mg_prolong_cell's order.
+template <bool PR>
+struct MgProWalk {};
+template <>
+struct MgProWalk<true> {
+  const double* eb;  // coarse row 0 at the lane's clamped column
+  int64_t iw, ie;    // the offsets of columns I - 1 and I + 1 from it (clamped)
+  bool west, east, px, py;
+  bool m[4];      // fine columns c - 1, c, c + 1, c + 2: inside B0's columns
+  double fc[4];   // 1 on a coarse column, 0.5 between two
+  double q[4];    // of the coarse row at or below the fine row that arrives next
+  __device__ __forceinline__ void rowq(double v, double vw, double ve, double o[4]) const {
+#pragma clang fp contract(off)
+    const double dl = dpp_from_lower(v), du = dpp_from_upper(v);  // by every lane, before the selects
+    const double lw = west ? vw : dl, le = east ? ve : du;
+    // px = 0: c - 1 between I - 1 and I, c on I, c + 1 between I and I + 1, c + 2 on I + 1
+    // px = 1: c - 1 on I - 1, c between I - 1 and I, c + 1 on I, c + 2 between I and I + 1
+    const double sw = lw + v, se = v + le;
+    o[0] = px ? lw : sw;
+    o[1] = px ? sw : v;
+    o[2] = px ? v : se;
+    o[3] = px ? se : le;
+  }
+  __device__ __forceinline__ void ldrow(const MgProArgs& a, int64_t J, double& v, double& vw, double& ve) const {
+    const double* p = eb + mg_clamp(J, a.jlo, a.jhi) * a.lde;
+    v = p[0];
+    vw = ve = 0.0;
+    if (west) vw = p[iw];
+    if (east) ve = p[ie];
+  }
+  // c: the lane's pair; w, e: it takes its W / E operands by loads of its own; [bl, bh): B0's columns;
+  // t0: the first fine row of the walk
+  __device__ __forceinline__ void init(const MgProArgs& a, int64_t c, bool w, bool e, int64_t bl, int64_t bh,
+                                       int64_t t0) {
+    west = w, east = e, px = a.px != 0, py = a.py != 0;
+    const int64_t I = c >> 1, Ic = mg_clamp(I, a.ilo, a.ihi);  // lanes outside re-read a cell inside (never used)
+    eb = a.e + Ic;
+    iw = mg_clamp(I - 1, a.ilo, a.ihi) - Ic;
+    ie = mg_clamp(I + 1, a.ilo, a.ihi) - Ic;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t x = c - 1 + k;
+      m[k] = x >= bl && x < bh;
+      fc[k] = ((x - a.px) & 1) == 0 ? 1.0 : 0.5;
+    }
+    double v, vw, ve;
+    ldrow(a, (t0 - a.py) >> 1, v, vw, ve);  // the coarse row at or below the first fine row
+    rowq(v, vw, ve, q);
+  }
+  // the coarse row above fine row t, when t lies between two
+  __device__ __forceinline__ void load(const MgProArgs& a, int64_t t, double& v, double& vw, double& ve) const {
+    v = vw = ve = 0.0;
+    if ((t - a.py) & 1) ldrow(a, ((t - a.py) >> 1) + 1, v, vw, ve);
+  }
+  __device__ __forceinline__ void row(int64_t t, bool rok, double v, double vw, double ve, d2& C, double& wn,
+                                      double& en) {
+#pragma clang fp contract(off)
+    const bool btw = ((t - py) & 1) != 0;  // wave-uniform
+    double qn[4] = {0.0, 0.0, 0.0, 0.0}, tq[4];
+    if (btw) rowq(v, vw, ve, qn);  // every lane of the wave or none: DPP
+    const double fr = btw ? 0.5 : 1.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double s2 = q[k] + qn[k];
+      const double s = btw ? s2 : q[k];
+      const double fk = fc[k] * fr;  // 1, 0.5 or 0.25: exact
+      tq[k] = fk * s;
+      q[k] = btw ? qn[k] : q[k];
+    }
+    const double cw = wn + tq[0], cx = C.x + tq[1], cy = C.y + tq[2], ce = en + tq[3];
+    wn = rok && m[0] ? cw : wn;
+    C.x = rok && m[1] ? cx : C.x;
+    C.y = rok && m[2] ? cy : C.y;
+    en = rok && m[3] ? ce : en;
+  }
+};
+
+template <int K, bool HAS_F, bool RB = false, bool PR = false>
+__global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgWalkArgs<PR> a) {
   constexpr int SH = mg_fuse_shift(K), OC = mg_fuse_wave_cols(K);
   constexpr int U = HAS_F ? kMgUnrollF : kMgUnrollP;
   const double* __restrict__ u = a.u;
@@ -236,9 +331,15 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
     A[l] = B[l] = fh[l] = d2{0.0, 0.0};
     wh[l] = eh[l] = 0.0;
   }
+  // PR: the lane's coarse column sits on fine column c + px of its pair, the other cell of the pair lies between
+  // it and the column of the W (px = 1) or E (px = 0) lane.  The four fine columns c - 1 .. c + 2 (the pair and the
+  // two one-lane loads): corrected or not, and q = what a coarse row gives them (its cell, or the sum of two).
+  MgProWalk<PR> pw;
+  if constexpr (PR) pw.init(a, c, west, east, hw ? -int64_t(K) : 0, nx + (he ? K : 0), r0 - K);
   for (int64_t tt = r0 - K; tt < r1 + K; tt += U) {
     d2 cn[U], fn[U];
     double wn[U], en[U];
+    [[maybe_unused]] double ec[U], ew[U], ee[U];
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       // rows past the read set are clamped to its last ones (loaded, not used)
@@ -257,6 +358,7 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
           if (fyo) fn[j].y = pf[c + 1];
         }
       }
+      if constexpr (PR) pw.load(a, tt + j, ec[j], ew[j], ee[j]);
     }
 #pragma unroll
     for (int j = 0; j < U; ++j) {
@@ -267,6 +369,8 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
         fh[0] = fn[j];
       }
       d2 C = cn[j];
+      if constexpr (PR)  // level 0 becomes u + P e on B0
+        pw.row(tr, tr >= (hs ? -int64_t(K) : 0) && tr < ny + (hn ? K : 0), ec[j], ew[j], ee[j], C, wn[j], en[j]);
       // red-black: level l + 1 is half-sweep l + 1 on row tr - 1 - l, and the lane's pair starts on an even
       // column, so which cell of the pair is due is one scalar for the row that arrives, the same at every level
       const bool duex = !RB || ((tr - 1 + a.par) & 1) == 0, duey = !RB || !duex;
@@ -300,8 +404,11 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_walk(const MgFuseArgs a) {
   }
 }
 
-template <int K, bool HAS_F, bool RB = false>
-__global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgFuseArgs a) {
+__device__ __forceinline__ double mg_prolong_cell(const double* __restrict__ e, int64_t lde, int64_t i, int64_t j,
+                                                  int px, int py, double u);
+
+template <int K, bool HAS_F, bool RB = false, bool PR = false>
+__global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgWalkArgs<PR> a) {
   const double* __restrict__ u = a.u;
   const double* __restrict__ f = a.f;
   const int64_t nx = a.nx, ny = a.ny;
@@ -321,7 +428,13 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgFuseArgs a)
       if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) <= K) {
         const int64_t X = x + dx, Y = y + dy;
         const bool in = X >= lo && X < hi && Y >= rlo && Y < rhi;
-        v[dy + K][dx + K] = in ? ub[Y * a.ld + X] : 0.0;
+        double c = in ? ub[Y * a.ld + X] : 0.0;
+        if constexpr (PR) {  // u + P e on B0
+          if (X >= (hw ? -int64_t(K) : 0) && X < nx + (he ? K : 0) && Y >= (hs ? -int64_t(K) : 0) &&
+              Y < ny + (hn ? K : 0))
+            c = mg_prolong_cell(a.e, a.lde, X, Y, a.px, a.py, c);
+        }
+        v[dy + K][dx + K] = c;
       }
 #pragma unroll
   for (int j = 1; j <= K; ++j) {
@@ -374,26 +487,26 @@ static bool mg_fuse_args_ok(int k, int64_t x0, int64_t nx, int64_t y0, int64_t n
   return !(ua < oe && oa < ub);
 }
 
-template <int K, bool HAS_F, bool RB = false>
-static int mg_smooth_k_launch(bool walk, MgFuseArgs a, hipStream_t s) {
+template <int K, bool HAS_F, bool RB = false, bool PR = false>
+static int mg_smooth_k_launch(bool walk, MgWalkArgs<PR> a, hipStream_t s) {
   if (walk) {
     const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(K)) * (kBlock / kWave);
     a.seg_rows = mg_fuse_seg_rows(K, a.nx, a.ny);
     a.nseg = (a.ny + a.seg_rows - 1) / a.seg_rows;
     a.nblocks = (a.nx + bc - 1) / bc * a.nseg;
     if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
-    mg_smooth_k_walk<K, HAS_F, RB><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
+    mg_smooth_k_walk<K, HAS_F, RB, PR><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
   } else {
     const int64_t nb = (a.nx * a.ny + kBlock - 1) / kBlock;
     if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_smooth_k_scalar<K, HAS_F, RB><<<grid_1d(nb), kBlock, 0, s>>>(a);
+    mg_smooth_k_scalar<K, HAS_F, RB, PR><<<grid_1d(nb), kBlock, 0, s>>>(a);
   }
   GMT_RET_LAUNCH();
 }
 
-template <int K, bool RB = false>
-static int mg_smooth_k_launch_f(bool walk, const MgFuseArgs& a, hipStream_t s) {
-  return a.f ? mg_smooth_k_launch<K, true, RB>(walk, a, s) : mg_smooth_k_launch<K, false, RB>(walk, a, s);
+template <int K, bool RB = false, bool PR = false>
+static int mg_smooth_k_launch_f(bool walk, const MgWalkArgs<PR>& a, hipStream_t s) {
+  return a.f ? mg_smooth_k_launch<K, true, RB, PR>(walk, a, s) : mg_smooth_k_launch<K, false, RB, PR>(walk, a, s);
 }
 
 // ---- full weighting ----
@@ -470,9 +583,9 @@ __global__ __launch_bounds__(kBlock) void mg_restrict_pt(int64_t x0, int64_t y0,
 __device__ __forceinline__ double mg_prolong_cell(const double* __restrict__ e, int64_t lde, int64_t i, int64_t j,
                                                   int px, int py, double u) {
 #pragma clang fp contract(off)
-  const int64_t di = i - px, dj = j - py;  // >= -1
+  const int64_t di = i - px, dj = j - py;  // >= -1 on a region; below that on the halo cells of gmt_mg_prolong_smooth
   const bool onx = (di & 1) == 0, ony = (dj & 1) == 0;
-  // the coarse column / row the cell sits on, else the one west / south of it (-1: the ring)
+  // the coarse column / row the cell sits on, else the one west / south of it (-1: the ring); both divisions are exact
   const int64_t I = onx ? di / 2 : (di + 1) / 2 - 1;
   const int64_t J = ony ? dj / 2 : (dj + 1) / 2 - 1;
   const double* p = e + J * lde + I;
@@ -971,6 +1084,100 @@ extern "C" int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t 
     case 2: return mg_smooth_k_launch_f<2, true>(walk, a, s);
     case 3: return mg_smooth_k_launch_f<3, true>(walk, a, s);
     default: return mg_smooth_k_launch_f<4, true>(walk, a, s);
+  }
+}
+
+// ---- the interpolation fused into h sweeps or half-sweeps (gmt_mg_prolong_smooth) ----
+
+namespace gmt {
+
+// gmt_mg_prolong_smooth takes these arguments (a non-empty region; h, rb, par, px, py and the mask in range);
+// *a gets the launch's arguments
+static bool mg_prolong_smooth_args(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
+                                   int mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
+                                   int64_t ld, const double* f, int64_t ldf, double c0, double c1, double om,
+                                   double* out, int64_t ldo, MgProArgs* a) {
+  if (!e || !mg_fuse_args_ok(h, x0, nx, y0, ny, mask, u, ld, f, ldf, out, ldo)) return false;
+  // the coarse cells that may be read: h/2 + 1 beyond the region's on a halo side, the ring on the others
+  const int64_t d = h / 2 + 1;
+  const int64_t cw = mask & GMT_MG_HALO_W ? d : 1, ce = mask & GMT_MG_HALO_E ? d : 1;
+  const int64_t cs = mask & GMT_MG_HALO_S ? d : 1, cn = mask & GMT_MG_HALO_N ? d : 1;
+  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
+  if (cx0 < cw || cy0 < cs || lde < cx0 + mx + ce) return false;
+  // out[R] against the read sets of e and f, as address ranges (u's: mg_fuse_args_ok)
+  const double* oa = out + y0 * ldo + x0;
+  const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
+  const double* ea = e + (cy0 - cs) * lde + (cx0 - cw);
+  const double* ee = e + (cy0 + my + cn - 1) * lde + (cx0 + mx + ce);
+  if (ea < oe && oa < ee) return false;
+  if (f) {
+    const int64_t gw = mask & GMT_MG_HALO_W ? h - 1 : 0, ge = mask & GMT_MG_HALO_E ? h - 1 : 0;
+    const int64_t gs = mask & GMT_MG_HALO_S ? h - 1 : 0, gn = mask & GMT_MG_HALO_N ? h - 1 : 0;
+    const double* fa = f + (y0 - gs) * ldf + (x0 - gw);
+    const double* fe = f + (y0 + ny + gn - 1) * ldf + (x0 + nx + ge);
+    if (fa < oe && oa < fe) return false;
+  }
+  if (a) {
+    static_cast<MgFuseArgs&>(*a) = MgFuseArgs{x0, nx, y0, ny, mask, u, ld, f, ldf, c0, c1, om, out, ldo, 0, 0, 0, par};
+    a->e = e + cy0 * lde + cx0;
+    a->lde = lde;
+    a->px = px, a->py = py;
+    a->ilo = -cw, a->ihi = mx - 1 + ce, a->jlo = -cs, a->jhi = my - 1 + cn;
+  }
+  return true;
+}
+
+static bool mg_prolong_smooth_range(int h, int rb, int par, int px, int py, int mask) {
+  return h >= 1 && h <= kMgMaxFuse && rb >= 0 && rb <= 1 && par >= 0 && par <= 1 && px >= 0 && px <= 1 && py >= 0 &&
+         py <= 1 && mask >= 0 && mask <= 15;
+}
+
+template <int K>
+static int mg_prolong_smooth_launch(bool rb, bool walk, const MgProArgs& a, hipStream_t s) {
+  return rb ? mg_smooth_k_launch_f<K, true, true>(walk, a, s) : mg_smooth_k_launch_f<K, false, true>(walk, a, s);
+}
+
+}  // namespace gmt
+
+extern "C" int gmt_mg_prolong_smooth_geom(int h, int64_t* wave_cols, int64_t* block_cols) {
+  return gmt_mg_smooth_k_geom(h, wave_cols, block_cols);
+}
+
+extern "C" int gmt_mg_prolong_smooth_path(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny,
+                                          int px, int py, int halo_mask, const double* e, int64_t cx0, int64_t cy0,
+                                          int64_t lde, const double* u, int64_t ld, const double* f, int64_t ldf,
+                                          const double* out, int64_t ldo, int64_t* seg_rows) {
+  using namespace gmt;
+  if (seg_rows) *seg_rows = 0;
+  if (!mg_prolong_smooth_range(h, rb, par, px, py, halo_mask) || nx < 0 || ny < 0) return GMT_PATH_NONE;
+  if (nx > 0 && ny > 0 &&
+      !mg_prolong_smooth_args(h, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f, ldf, 0.0, 0.0, 0.0,
+                              const_cast<double*>(out), ldo, nullptr))
+    return GMT_PATH_NONE;
+  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);  // e is read 8 B per lane: no rule of its own
+  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(h, nx, ny);
+  return path;
+}
+
+extern "C" int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px,
+                                     int py, int halo_mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde,
+                                     const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
+                                     double omega, double* out, int64_t ldo, void* stream) {
+  using namespace gmt;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!mg_prolong_smooth_range(h, rb, par, px, py, halo_mask) || nx < 0 || ny < 0)
+    return static_cast<int>(hipErrorInvalidValue);
+  if (nx == 0 || ny == 0) return 0;
+  MgProArgs a;
+  if (!mg_prolong_smooth_args(h, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f, ldf, c0, c1,
+                              omega, out, ldo, &a))
+    return static_cast<int>(hipErrorInvalidValue);
+  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
+  switch (h) {
+    case 1: return mg_prolong_smooth_launch<1>(rb != 0, walk, a, s);
+    case 2: return mg_prolong_smooth_launch<2>(rb != 0, walk, a, s);
+    case 3: return mg_prolong_smooth_launch<3>(rb != 0, walk, a, s);
+    default: return mg_prolong_smooth_launch<4>(rb != 0, walk, a, s);
   }
 }
 

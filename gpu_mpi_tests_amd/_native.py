@@ -207,6 +207,17 @@ _SIGS = {
         [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp],
     ),
     "gmt_mg_resid_restrict_geom": (c_int, [c_vp, c_vp]),
+    "gmt_mg_prolong_smooth": (
+        c_int,
+        [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64,
+         c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp, c_i64, c_vp],
+    ),
+    "gmt_mg_prolong_smooth_path": (
+        c_int,
+        [c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64,
+         c_vp, c_i64, c_vp, c_i64, c_vp],
+    ),
+    "gmt_mg_prolong_smooth_geom": (c_int, [c_int, c_vp, c_vp]),
     "gmt_mg_prolong_add": (
         c_int,
         [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],

@@ -104,7 +104,8 @@ class MgOpts(ctypes.Structure):
                 ("max_cycles", ctypes.c_int), ("check_every", ctypes.c_int), ("lag", ctypes.c_int),
                 ("nu1", ctypes.c_int), ("nu2", ctypes.c_int), ("omega", ctypes.c_double),
                 ("max_levels", ctypes.c_int), ("coarse_iters", ctypes.c_int), ("coarsen", ctypes.c_int),
-                ("fuse", ctypes.c_int), ("smoother", ctypes.c_int), ("fuse_resid", ctypes.c_int)]
+                ("fuse", ctypes.c_int), ("smoother", ctypes.c_int), ("fuse_resid", ctypes.c_int),
+                ("fuse_prolong", ctypes.c_int)]
 
 
 class MgResult(ctypes.Structure):
@@ -116,7 +117,8 @@ class MgResult(ctypes.Structure):
                 ("coarse_iters", ctypes.c_int), ("coarse_rho", ctypes.c_double),
                 ("fuse", ctypes.c_int), ("fuse_fine", ctypes.c_int), ("fuse_levels", ctypes.c_int),
                 ("smoother", ctypes.c_int), ("fuse_resid", ctypes.c_int), ("resid_levels", ctypes.c_int),
-                ("resid_mask", ctypes.c_int)]
+                ("resid_mask", ctypes.c_int), ("fuse_prolong", ctypes.c_int), ("prolong_levels", ctypes.c_int),
+                ("prolong_mask", ctypes.c_int)]
 
 
 NORMS = {"l2": 0, "max": 1}  # SolveOpts::norm
@@ -705,7 +707,7 @@ class NativeJacobi:
     def mg(self, tol: float = 0.0, rtol: float = 0.0, norm: str = "l2", max_cycles: int = 0, check_every: int = 0,
            lag: int = 1, nu: tuple = (2, 2), omega: "float | None" = None, max_levels: int = 0,
            coarse_iters: int = 0, coarsen: str = "nested", fuse: int = 0, smoother: str = "jacobi",
-           fuse_resid: bool = False) -> dict:
+           fuse_resid: bool = False, fuse_prolong: bool = False) -> dict:
         """Geometric multigrid V-cycles from the current field
         (JacobiSolver::mg; :func:`serial_mg` is the definition): ``nu[0]`` /
         ``nu[1]`` damped Jacobi sweeps ``u + omega*(G(u) - u)`` before / after
@@ -749,6 +751,11 @@ class NativeJacobi:
         same bits, on every level :func:`mg_resid_levels` lists; the other
         levels run the two kernels.  ``resid_levels`` lists the levels that
         ran fused.
+        ``fuse_prolong=True`` interpolates inside the first pass of the
+        post-smoothing run (gmt_mg_prolong_smooth instead of gmt_mg_prolong_add
+        and that pass), for the same bits, on every level
+        :func:`mg_prolong_levels` lists; the other levels run the two kernels.
+        ``prolong_levels`` lists the levels that ran fused.
         Identical on every rank.  ValueError on bad options, a periodic axis,
         or a problem with no coarse level (``nx + 1`` or ``ny + 1`` odd, or a
         rank that would own no coarse point).  Collective."""
@@ -776,10 +783,12 @@ class NativeJacobi:
             raise ValueError(f"coarsen must be one of {sorted(COARSEN)}, got {coarsen!r}")
         if isinstance(fuse, bool) or int(fuse) != fuse or not (int(fuse) == 0 or 2 <= int(fuse) <= MG_MAX_FUSE):
             raise ValueError(f"fuse must be 0 or 2..{MG_MAX_FUSE}, got {fuse!r}")
+        if fuse_prolong not in (False, True):
+            raise ValueError(f"fuse_prolong must be False or True, got {fuse_prolong!r}")
         o = MgOpts(tol=tol, rtol=rtol, norm=NORMS[norm], max_cycles=int(max_cycles), check_every=every, lag=int(lag),
                    nu1=nu1, nu2=nu2, omega=omega, max_levels=int(max_levels), coarse_iters=int(coarse_iters),
                    coarsen=COARSEN[coarsen], fuse=int(fuse), smoother=SMOOTHERS[smoother],
-                   fuse_resid=int(bool(fuse_resid)))
+                   fuse_resid=int(bool(fuse_resid)), fuse_prolong=int(fuse_prolong))
         r = MgResult()
         rc = self.lib.gmt_engine_jacobi_mg(self.h, ctypes.byref(o), ctypes.byref(r))
         if rc == 2:
@@ -797,6 +806,9 @@ class NativeJacobi:
         out["fuse_resid"] = bool(r.fuse_resid)
         out["resid_levels"] = [l for l in range(r.levels) if r.resid_mask >> l & 1]
         del out["resid_mask"]
+        out["fuse_prolong"] = bool(r.fuse_prolong)
+        out["prolong_levels"] = [l for l in range(r.levels) if r.prolong_mask >> l & 1]
+        del out["prolong_mask"]
         return out
 
     def interior(self) -> np.ndarray:
@@ -1253,6 +1265,35 @@ def mg_resid_levels(ny: int, nx: int, dims: tuple, ghost: int, max_levels: int =
         if ok and ranks > 1:
             ok = all(b1 - b0 >= 2 for b in (by, bx) if len(b) > 2 for b0, b1 in zip(b, b[1:]))
             ok = ok and (l > 0 or int(ghost) >= 2)
+        if ok:
+            out.append(l)
+    return out
+
+
+def mg_prolong_levels(ny: int, nx: int, dims: tuple, ghost: int, fuse: int = 0, nu2: int = 2,
+                      smoother: str = "jacobi", max_levels: int = 0, coarsen: str = "nested") -> list:
+    """The levels of ``mg(fuse_prolong=True)`` whose interpolation runs inside
+    the first post-smoothing pass (gmt_mg_prolong_smooth).  With ``n2 = nu2``
+    sweeps (``2 * nu2`` half-sweeps for ``smoother="rb"``) and
+    ``c = min(n2, d)``, ``d`` the level's depth from :func:`mg_fuse_depths`, a
+    level of :func:`mg_levels` that interpolates fuses iff ``nu2 >= 1``, both
+    its extents are odd (its transfer is not table-driven), and there is one
+    rank or every rank owns at least ``c // 2 + 1`` cells of the next coarser
+    level on each axis of the ``dims = (py, px)`` grid with more than one rank.
+    The Python model of gmt::mg_prolong_levels."""
+    if smoother not in SMOOTHERS:
+        raise ValueError(f"smoother must be one of {sorted(SMOOTHERS)}, got {smoother!r}")
+    shares = []
+    levels = mg_levels(ny, nx, dims, max_levels, coarsen, shares)
+    depths = mg_fuse_depths(ny, nx, dims, fuse, ghost, max_levels, coarsen)
+    ranks = int(dims[0]) * int(dims[1])
+    n2 = int(nu2) * (2 if smoother == "rb" else 1)
+    out = []
+    for l, ((my, mx), d) in enumerate(zip(levels[:-1], depths)):
+        ok = int(nu2) >= 1 and my % 2 == 1 and mx % 2 == 1
+        if ok and ranks > 1:
+            w = min(n2, d) // 2 + 1
+            ok = all(b1 - b0 >= w for b in shares[l + 1] if len(b) > 2 for b0, b1 in zip(b, b[1:]))
         if ok:
             out.append(l)
     return out

@@ -11,7 +11,8 @@ the multigrid smoother and grid transfers ``mg_smooth`` / ``mg_restrict`` /
 ``mg_prolong_add``, the fused smoother ``mg_smooth_k`` (k sweeps per memory
 pass), the red-black Gauss-Seidel smoother ``mg_smooth_rb`` (h coloured
 half-sweeps per memory pass), the fused residual + restriction
-``mg_resid_restrict``, the table-driven transfers for levels that are not nested
+``mg_resid_restrict``, the fused interpolation + smoothing pass
+``mg_prolong_smooth``, the table-driven transfers for levels that are not nested
 ``mg_restrict_tab`` / ``mg_prolong_add_tab``, and ``jacobi5tb`` (K fused sweeps
 per memory pass).
 """
@@ -49,6 +50,9 @@ from .kernels import (  # noqa: F401
     mg_prolong_add_path,
     mg_prolong_add_tab,
     mg_prolong_add_tab_path,
+    mg_prolong_smooth,
+    mg_prolong_smooth_geom,
+    mg_prolong_smooth_path,
     mg_resid_restrict,
     mg_resid_restrict_geom,
     mg_resid_restrict_path,

@@ -772,6 +772,62 @@ def mg_resid_restrict_geom() -> tuple[int, int]:
     return int(wc.value), int(bc.value)
 
 
+def mg_prolong_smooth(e: torch.Tensor, u: torch.Tensor, out: torch.Tensor, omega: float,
+                      region: tuple[int, int, int, int], parity: tuple[int, int], coarse: tuple[int, int], h: int,
+                      rb: int = 0, par: int = 0, halo_mask: int = 0, f: torch.Tensor | None = None, c0: float = 0.25,
+                      c1: float = 1.0) -> torch.Tensor:
+    """The interpolation ``u + P e`` and the first ``h`` (1..4) sweeps
+    (``rb = 0``, :func:`mg_smooth_k`) or coloured half-sweeps (``rb = 1``,
+    :func:`mg_smooth_rb` with ``par``) of the result in one memory pass
+    (gmt_mg_prolong_smooth).  The correction is :func:`mg_prolong_add`'s cell
+    rule on the region grown by ``h`` cells on every side whose bit is set in
+    ``halo_mask``; the fixed ring of ``u`` enters as it is.  ``u`` and ``e`` are
+    read only.  Bitwise :func:`reference.mg_prolong_smooth`.  ``out`` must not
+    share storage with ``u``, ``e`` or ``f``.  Returns ``out``."""
+    _check2d(e, "mg_prolong_smooth.e")
+    _check2d(u, "mg_prolong_smooth.u")
+    _check2d(out, "mg_prolong_smooth.out")
+    if f is not None:
+        _check2d(f, "mg_prolong_smooth.f")
+    if _overlap(u, out) or _overlap(e, out) or (f is not None and _overlap(f, out)):
+        raise ValueError("mg_prolong_smooth: out must not share storage with u, e or f")
+    x0, nx, y0, ny = (int(t) for t in region)
+    (px, py), (cx0, cy0) = (int(t) for t in parity), (int(t) for t in coarse)
+    if not _is_dev(out):
+        return ref.mg_prolong_smooth(e, u, out, omega, x0, nx, y0, ny, px, py, cx0, cy0, int(h), int(rb), int(par),
+                                     int(halo_mask), f, c0, c1)
+    _native.check(_native.lib().gmt_mg_prolong_smooth(int(h), int(rb), int(par), x0, nx, y0, ny, px, py,
+                                                      int(halo_mask), e.data_ptr(), cx0, cy0, e.stride(0),
+                                                      u.data_ptr(), u.stride(0), *_ptr_ld(f), float(c0), float(c1),
+                                                      float(omega), out.data_ptr(), out.stride(0), _stream(out)),
+                  "gmt_mg_prolong_smooth")
+    return out
+
+
+def mg_prolong_smooth_path(e: torch.Tensor, u: torch.Tensor, out: torch.Tensor, region: tuple[int, int, int, int],
+                           parity: tuple[int, int], coarse: tuple[int, int], h: int, rb: int = 0, par: int = 0,
+                           halo_mask: int = 0, f: torch.Tensor | None = None) -> tuple[int, int]:
+    """The kernel :func:`mg_prolong_smooth` would launch (gmt_mg_prolong_smooth_path,
+    no launch): ``(PATH_ROW_WALK or PATH_SCALAR, output rows per segment of the walk)``."""
+    x0, nx, y0, ny = (int(t) for t in region)
+    seg = ctypes.c_int64(0)
+    path = _native.lib().gmt_mg_prolong_smooth_path(int(h), int(rb), int(par), x0, nx, y0, ny, int(parity[0]),
+                                                    int(parity[1]), int(halo_mask), e.data_ptr(), int(coarse[0]),
+                                                    int(coarse[1]), e.stride(0), u.data_ptr(), u.stride(0),
+                                                    *_ptr_ld(f), out.data_ptr(), out.stride(0),
+                                                    ctypes.cast(ctypes.pointer(seg), ctypes.c_void_p))
+    return int(path), int(seg.value)
+
+
+def mg_prolong_smooth_geom(h: int) -> tuple[int, int]:
+    """``(output columns per wave, per workgroup)`` of the fused pass's walk (gmt_mg_prolong_smooth_geom)."""
+    wc, bc = ctypes.c_int64(0), ctypes.c_int64(0)
+    if _native.lib().gmt_mg_prolong_smooth_geom(int(h), ctypes.cast(ctypes.pointer(wc), ctypes.c_void_p),
+                                                ctypes.cast(ctypes.pointer(bc), ctypes.c_void_p)) != 0:
+        raise ValueError(f"mg_prolong_smooth_geom: h = {h} outside 1..4")
+    return int(wc.value), int(bc.value)
+
+
 def mg_prolong_add(e: torch.Tensor, u: torch.Tensor, region: tuple[int, int, int, int], parity: tuple[int, int],
                    coarse: tuple[int, int]) -> torch.Tensor:
     """``u += P e`` over the fine ``region = (x0, nx, y0, ny)``, P the bilinear

@@ -342,6 +342,35 @@ def mg_prolong_add(e, u, x0: int, nx: int, y0: int, ny: int, px: int, py: int, c
     return u
 
 
+def mg_prolong_smooth(e, u, out, omega: float, x0: int, nx: int, y0: int, ny: int, px: int, py: int, cx0: int,
+                      cy0: int, h: int, rb: int = 0, par: int = 0, halo_mask: int = 0, f=None, c0: float = 0.25,
+                      c1: float = 1.0):
+    """gmt_mg_prolong_smooth: :func:`mg_prolong_add` over a copy of ``u`` on the
+    region grown by ``h`` cells on every side whose bit is set in ``halo_mask``,
+    then :func:`mg_smooth_k` (``rb = 0``) or :func:`mg_smooth_rb` (``rb = 1``)
+    with ``h`` of that copy into ``out``.  The grown region starts ``g`` cells
+    earlier, so its parity and first coarse cell move with it: every fine cell
+    keeps its coarse column and row."""
+    if not 1 <= h <= MG_MAX_FUSE or not 0 <= halo_mask <= 15 or rb not in (0, 1) or par not in (0, 1) \
+            or px not in (0, 1) or py not in (0, 1):
+        raise ValueError("mg_prolong_smooth: h, rb, par, px, py or the mask out of range")
+    if nx < 0 or ny < 0:
+        raise ValueError("mg_prolong_smooth: negative extent")
+    if nx > 0 and ny > 0:
+        v = u.clone() if hasattr(u, "clone") else u.copy()
+        gw, ge = (h if halo_mask & MG_HALO_W else 0), (h if halo_mask & MG_HALO_E else 0)
+        gs, gn = (h if halo_mask & MG_HALO_S else 0), (h if halo_mask & MG_HALO_N else 0)
+        # the first coarse point at or after the grown region's first cell: parity p', coarse index (p' - g - p) / 2
+        qx, qy = (px + gw) % 2, (py + gs) % 2
+        mg_prolong_add(e, v, x0 - gw, nx + gw + ge, y0 - gs, ny + gs + gn, qx, qy,
+                       cx0 + (qx - gw - px) // 2, cy0 + (qy - gs - py) // 2)
+        if rb:
+            mg_smooth_rb(v, out, omega, x0, nx, y0, ny, h, par, halo_mask, f, c0, c1)
+        else:
+            mg_smooth_k(v, out, omega, x0, nx, y0, ny, h, halo_mask, f, c0, c1)
+    return out
+
+
 def _np_view(a):
     """A NumPy view of a CPU tensor's storage (the array itself for NumPy)."""
     return a.numpy() if isinstance(a, torch.Tensor) else a
