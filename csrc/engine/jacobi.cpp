@@ -491,6 +491,8 @@ void JacobiSolver::enqueue_step(int parity) {
 }
 
 int JacobiSolver::halo_mask() const {
+  static_assert(GMT_MG_HALO_W == 1 && GMT_MG_HALO_E == 2 && GMT_MG_HALO_S == 4 && GMT_MG_HALO_N == 8,
+                "the gmt_mg_* calls take this mask too");
   return (nb_.west >= 0 ? 1 : 0) | (nb_.east >= 0 ? 2 : 0) | (nb_.south >= 0 ? 4 : 0) |
          (nb_.north >= 0 ? 8 : 0);
 }
@@ -1215,10 +1217,7 @@ CgResult JacobiSolver::cg(const CgOpts& o) {
     double* rr = sc + 2 * (k & 1);
     double* rn = sc + 2 * ((k & 1) ^ 1);
     double* pq = sc + 4;
-    if (cg_halo_->active()) {
-      cg_halo_->start(s_);
-      cg_halo_->finish(s_);
-    }
+    cg_halo_->enqueue(s_);
     GMT_CHECK("cg apply", gmt_cg_apply(0, xo_, nx_, yo_, ny_, cg_p_.data(), ld_, nullptr, 0, kC0, 0.0, cg_q_.data(),
                                        ld_, pq, cg_ws_.data(), s_));
     allreduce_sum_max(pq);
@@ -1295,11 +1294,7 @@ ChebyResult JacobiSolver::cheby(const ChebyOpts& o) {
   bool ring = false;  // the current buffer's 1-wide faces hold the neighbours' current values
   auto exchange = [&] {
     if (ring || fresh_[parity_]) return;
-    Halo2D& h = *cheby_halo_[parity_];
-    if (h.active()) {
-      h.start(s_);
-      h.finish(s_);
-    }
+    cheby_halo_[parity_]->enqueue(s_);
     ring = true;
   };
   // iteration k + 1 of this call (k = 0: the plain sweep, w_1 = 1)
@@ -1356,6 +1351,8 @@ namespace {
 struct MgShape {
   int64_t ny = 0, nx = 0;
   std::vector<int64_t> by, bx;
+  // an even extent: no nested coarser level, the transfers to the next one go by tables
+  bool tab() const { return ny % 2 == 0 || nx % 2 == 0; }
 };
 
 std::vector<int64_t> mg_bounds(int64_t n, int p) {
@@ -1401,15 +1398,14 @@ std::vector<MgShape> mg_hierarchy(int64_t ny, int64_t nx, int py, int px, int ma
     const MgShape& f = out.back();
     MgShape c;
     if (coarsen == 0) {
-      if (f.ny % 2 == 0 || f.nx % 2 == 0) break;
+      if (f.tab()) break;
       c.by = f.by, c.bx = f.bx;
       if (!halve(c.by) || !halve(c.bx)) break;
       c.ny = (f.ny - 1) / 2, c.nx = (f.nx - 1) / 2;
     } else {
       c.ny = mg_coarse_extent(f.ny), c.nx = mg_coarse_extent(f.nx);
       if (c.ny < 1 || c.nx < 1) break;
-      const bool tables = f.ny % 2 == 0 || f.nx % 2 == 0;
-      if (!mg_any_axis(f.ny, c.ny, f.by, tables, &c.by) || !mg_any_axis(f.nx, c.nx, f.bx, tables, &c.bx)) break;
+      if (!mg_any_axis(f.ny, c.ny, f.by, f.tab(), &c.by) || !mg_any_axis(f.nx, c.nx, f.bx, f.tab(), &c.bx)) break;
     }
     out.push_back(std::move(c));
   }
@@ -1468,7 +1464,7 @@ std::vector<int> mg_prolong_levels(int64_t ny, int64_t nx, int py, int px, int g
   std::vector<int> out;
   for (size_t l = 0; l + 1 < shapes.size(); ++l) {
     const int d = mg_fuse_depth(fuse, mg_min_share(shapes[l].by), mg_min_share(shapes[l].bx), l == 0, py * px, ghost);
-    out.push_back(mg_prolong_level(shapes[l].ny % 2 == 0 || shapes[l].nx % 2 == 0, nu2,
+    out.push_back(mg_prolong_level(shapes[l].tab(), nu2,
                                    mg_prolong_chunk(nu2, smoother, d), mg_min_share(shapes[l + 1].by),
                                    mg_min_share(shapes[l + 1].bx), py * px));
   }
@@ -1479,8 +1475,8 @@ std::vector<int> mg_resid_levels(int64_t ny, int64_t nx, int py, int px, int gho
   const auto shapes = mg_hierarchy(ny, nx, py, px, max_levels, coarsen);
   std::vector<int> out;
   for (size_t l = 0; l + 1 < shapes.size(); ++l)
-    out.push_back(mg_resid_level(shapes[l].ny % 2 == 0 || shapes[l].nx % 2 == 0, mg_min_share(shapes[l].by),
-                                 mg_min_share(shapes[l].bx), l == 0, py * px, ghost));
+    out.push_back(mg_resid_level(shapes[l].tab(), mg_min_share(shapes[l].by), mg_min_share(shapes[l].bx), l == 0,
+                                 py * px, ghost));
   return out;
 }
 
@@ -1542,7 +1538,7 @@ void JacobiSolver::mg_setup() {
     }
     L.dyo = L.yo, L.dld = L.ld;
     if (l + 1 == mg.size()) continue;
-    L.tab = L.ny_g % 2 == 0 || L.nx_g % 2 == 0;
+    L.tab = shapes[l].tab();
     if (L.tab) {  // room for the 2-wide ring of d, whatever the engine's ghost depth
       L.dyo = std::max<int64_t>(L.yo, kMgTapHalo);
       L.dld = std::max(L.ld, round_up(L.xo + L.nx + kMgTapHalo, 64));
@@ -1572,11 +1568,7 @@ void JacobiSolver::mg_setup() {
 void JacobiSolver::mg_ring(int l) {
   MgLevel& L = mg_[mgh_][l];
   if (L.ring) return;
-  Halo2D& h = l == 0 ? *cheby_halo_[L.cur] : *L.hu[L.cur];
-  if (h.active()) {
-    h.start(s_);
-    h.finish(s_);
-  }
+  (l == 0 ? *cheby_halo_[L.cur] : *L.hu[L.cur]).enqueue(s_);
   L.ring = true;
 }
 
@@ -1621,11 +1613,7 @@ void JacobiSolver::mg_fuse_setup(int levels, const MgOpts& o) {
   }
   MgLevel& F = mg[0];
   if (F.sw > 0 && F.sp && t_.size() > 1 && f_ring_ < F.sw) {
-    Halo2D& h = *F.hs[F.sw];
-    if (h.active()) {
-      h.start(s_);
-      h.finish(s_);
-    }
+    F.hs[F.sw]->enqueue(s_);
     f_ring_ = F.sw;
   }
 }
@@ -1637,8 +1625,7 @@ void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o, int done) {
   MgLevel& L = mg_[mgh_][l];
   const int64_t ldf = L.sp ? L.ld : 0;
   const double c1 = L.sp ? 1.0 : 0.0;
-  const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
-                   (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+  const int mask = halo_mask();
   const bool rb = o.smoother == 1;
   // cell (xo, yo) has the 1-based global indices (ox + 1, oy + 1): red, due first, iff ox + oy is even
   int par = static_cast<int>((L.ox + L.oy) & 1);
@@ -1647,34 +1634,19 @@ void JacobiSolver::mg_smooth_run(int l, int n, const MgOpts& o, int done) {
   par ^= done & 1;
   while (n > 0) {
     const int c = std::min(n, L.depth);
+    // a rank without neighbours reads its fixed ring only: its ring plan exchanges nothing
+    if (c >= 2 && mask != 0)
+      L.hk[L.cur][L.depth]->enqueue(s_);
+    else
+      mg_ring(l);
     if (rb) {
-      if (c >= 2) {
-        if (mask != 0) {
-          Halo2D& h = *L.hk[L.cur][L.depth];
-          if (h.active()) {
-            h.start(s_);
-            h.finish(s_);
-          }
-        }
-      } else {
-        mg_ring(l);
-      }
       GMT_CHECK("mg red-black smooth", gmt_mg_smooth_rb(c, par, L.xo, L.nx, L.yo, L.ny, mask, L.up[L.cur], L.ld, L.sp,
                                                         ldf, kC0, c1, o.omega, L.up[L.cur ^ 1], L.ld, s_));
       par ^= c & 1;
     } else if (c >= 2) {
-      // a rank without neighbours reads its fixed ring only
-      if (mask != 0) {
-        Halo2D& h = *L.hk[L.cur][L.depth];
-        if (h.active()) {
-          h.start(s_);
-          h.finish(s_);
-        }
-      }
       GMT_CHECK("mg fused smooth", gmt_mg_smooth_k(c, L.xo, L.nx, L.yo, L.ny, mask, L.up[L.cur], L.ld, L.sp, ldf, kC0,
                                                    c1, o.omega, L.up[L.cur ^ 1], L.ld, s_));
     } else {
-      mg_ring(l);
       GMT_CHECK("mg smooth", gmt_mg_smooth(L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, o.omega,
                                            L.up[L.cur ^ 1], L.ld, s_));
     }
@@ -1710,19 +1682,13 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
   auto smooth = [&](int n) { mg_smooth_run(l, n, o); };
   MgLevel& C = mg_[mgh_][l + 1];
   const int px = L.ox % 2 == 0 ? 1 : 0, py = L.oy % 2 == 0 ? 1 : 0;
+  const int mask = halo_mask();  // a rank without neighbours reads its fixed rings only
   smooth(o.nu1);
   if (L.resid) {
-    // the residual on the ring of d comes from the neighbours' cells two deep; a rank without neighbours
-    // reads its fixed ring only
-    const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
-                     (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+    // the residual on the ring of d comes from the neighbours' cells two deep
     if (mask != 0) {
       // a level that interpolates inside its post-smoothing pass reads this halo again, c deep: max(2, c) wide
-      Halo2D& h = *L.hk[L.cur][L.prolong && L.pc >= 2 ? L.pc : 2];
-      if (h.active()) {
-        h.start(s_);
-        h.finish(s_);
-      }
+      L.hk[L.cur][L.prolong && L.pc >= 2 ? L.pc : 2]->enqueue(s_);
       L.ring = true;
     }
     GMT_CHECK("mg fused residual and restrict",
@@ -1734,10 +1700,7 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
     double* dv = L.d.data() + (L.dyo - L.yo) * L.dld;
     GMT_CHECK("mg residual", gmt_cg_apply(1, L.xo, L.nx, L.yo, L.ny, L.up[L.cur], L.ld, L.sp, ldf, kC0, c1, dv, L.dld,
                                           mg_ws_.data(), mg_ws_.data() + 2, s_));
-    if (L.hd->active()) {
-      L.hd->start(s_);
-      L.hd->finish(s_);
-    }
+    L.hd->enqueue(s_);
     if (L.tab)
       GMT_CHECK("mg restrict", gmt_mg_restrict_tab(L.plan.get(), L.xo, L.dyo, L.d.data(), L.dld, C.s.data(), C.xo,
                                                    C.yo, C.ld, s_));
@@ -1746,10 +1709,7 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
                                                C.yo, C.ld, s_));
   }
   // a coarser level with fused smoothing or a fused transfer reads the ring of its source too
-  if (C.sw > 0 && C.hs[C.sw] && C.hs[C.sw]->active()) {
-    C.hs[C.sw]->start(s_);
-    C.hs[C.sw]->finish(s_);
-  }
+  if (C.sw > 0 && C.hs[C.sw]) C.hs[C.sw]->enqueue(s_);
   // u = 0 on the coarser level, ring included: current on every rank
   GMT_CHECK("memset", gmt_rt_memset_async(C.up[0], 0, C.u[0].bytes(), s_));
   C.cur = 0;
@@ -1757,25 +1717,12 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
   mg_cycle(l + 1, levels, o, coarse_iters, coarse_rho);
   if (L.prolong) {
     // u + P e inside the first chunk of the post-smoothing run: the halo cells of u are corrected here as
-    // their owners would, from the coarser field c/2 + 1 beyond this rank's cells; a rank without neighbours
-    // reads its fixed rings only
-    const int mask = (nb_.west >= 0 ? GMT_MG_HALO_W : 0) | (nb_.east >= 0 ? GMT_MG_HALO_E : 0) |
-                     (nb_.south >= 0 ? GMT_MG_HALO_S : 0) | (nb_.north >= 0 ? GMT_MG_HALO_N : 0);
+    // their owners would, from the coarser field c/2 + 1 beyond this rank's cells
     const int c = L.pc, cw = c / 2 + 1;
     if (mask != 0) {
-      Halo2D& hc = cw >= 2 ? *C.hk[C.cur][cw] : *C.hu[C.cur];  // either with corners
-      if (hc.active()) {
-        hc.start(s_);
-        hc.finish(s_);
-      }
+      (cw >= 2 ? *C.hk[C.cur][cw] : *C.hu[C.cur]).enqueue(s_);  // either with corners
       C.ring = true;
-      if (c >= 2 && !L.resid) {  // the fused residual left the halo this deep already
-        Halo2D& h = *L.hk[L.cur][c];
-        if (h.active()) {
-          h.start(s_);
-          h.finish(s_);
-        }
-      }
+      if (c >= 2 && !L.resid) L.hk[L.cur][c]->enqueue(s_);  // the fused residual left the halo this deep already
     }
     // c = 1: the faces are current since the residual.  Level 0's ring plan has no corners: the kernel corrects
     // the four corner cells of B0 from stale values, and one sweep's plus-shaped stencil never reads them
@@ -1790,11 +1737,7 @@ void JacobiSolver::mg_cycle(int l, int levels, const MgOpts& o, int coarse_iters
     mg_smooth_run(l, o.nu2, o, c);
     return;
   }
-  Halo2D& hc = *C.hu[C.cur];
-  if (hc.active()) {
-    hc.start(s_);
-    hc.finish(s_);
-  }
+  C.hu[C.cur]->enqueue(s_);
   C.ring = true;
   if (L.tab)
     GMT_CHECK("mg prolong", gmt_mg_prolong_add_tab(L.plan.get(), L.xo, L.yo, C.up[C.cur], C.xo, C.yo, C.ld,
@@ -1843,13 +1786,14 @@ MgResult JacobiSolver::mg(const MgOpts& o) {
   res.fuse = o.fuse;
   res.smoother = o.smoother;
   res.fuse_fine = F.depth;
-  for (int l = 0; l + 1 < levels; ++l) res.fuse_levels += mg_[mgh_][l].depth >= 2;
   res.fuse_resid = o.fuse_resid;
-  for (int l = 0; l + 1 < levels; ++l)
-    if (mg_[mgh_][l].resid) ++res.resid_levels, res.resid_mask |= 1 << l;
   res.fuse_prolong = o.fuse_prolong;
-  for (int l = 0; l + 1 < levels; ++l)
-    if (mg_[mgh_][l].prolong) ++res.prolong_levels, res.prolong_mask |= 1 << l;
+  for (int l = 0; l + 1 < levels; ++l) {
+    const MgLevel& L = mg_[mgh_][l];
+    res.fuse_levels += L.depth >= 2;
+    if (L.resid) ++res.resid_levels, res.resid_mask |= 1 << l;
+    if (L.prolong) ++res.prolong_levels, res.prolong_mask |= 1 << l;
+  }
   F.cur = parity_;
   F.ring = fresh_[parity_];
   run_checks(loop, res,

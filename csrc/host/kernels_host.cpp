@@ -20,8 +20,11 @@
 #include <vector>
 
 #include "gmt/kernels.h"
+#include "gmt/mg_args.hpp"
 #include "gmt/mg_tab.hpp"
 #include "gmt/tb_geom.h"
+
+using gmt::MgCheck;
 
 extern "C" {
 
@@ -438,8 +441,8 @@ int gmt_cheby_step(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double*
   return 0;
 }
 
-// the multigrid kernels (csrc/kernels/mg.hip): the same checks, codes and cell
-// expressions (this file is built with -ffp-contract=off)
+// the multigrid kernels (csrc/kernels/mg.hip): the checks they run (gmt/mg_args.hpp),
+// the same codes and cell expressions (this file is built with -ffp-contract=off)
 int gmt_mg_smooth_path(int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*,
                        int64_t, int64_t* seg_rows) {
   if (seg_rows) *seg_rows = 0;
@@ -450,9 +453,8 @@ int gmt_mg_prolong_add_path(int64_t, const double*, int64_t, const double*, int6
 
 int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* u, int64_t ld, const double* f,
                   int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo, void*) {
-  if (nx < 0 || ny < 0) return 1;
-  if (nx == 0 || ny == 0) return 0;
-  if (!u || !out || x0 < 1 || y0 < 1 || ld < x0 + nx + 1 || ldo < x0 + nx || (f && ldf < x0 + nx)) return 1;
+  const MgCheck chk = gmt::mg_smooth_check(x0, nx, y0, ny, u, ld, f, ldf, out, ldo);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   for (int64_t y = y0; y < y0 + ny; ++y)
     for (int64_t x = x0; x < x0 + nx; ++x) {
       const double* c = u + y * ld + x;
@@ -467,10 +469,9 @@ int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, const double* 
 
 // k fused sweeps: the definition, on a copy of u's read set
 int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols) {
-  if (k < 1 || k > GMT_MG_MAX_FUSE) return 1;
-  const int64_t wc = k == 1 ? 128 : 128 - 2 * (k / 2 * 2);  // the gfx950 kernel's (csrc/kernels/mg.hip)
-  if (wave_cols) *wave_cols = wc;
-  if (block_cols) *block_cols = 4 * wc;
+  if (!gmt::mg_depth_ok(k)) return 1;
+  if (wave_cols) *wave_cols = gmt::mg_fuse_wave_cols(k);  // the gfx950 kernel's (csrc/kernels/mg.hip)
+  if (block_cols) *block_cols = gmt::mg_fuse_block_cols(k);
   return 0;
 }
 
@@ -508,26 +509,15 @@ struct HostProlong {
   int px, py;
 };
 
-// rb: only the cells due in half-sweep j are updated (gmt_mg_smooth_rb's colour rule); pro: level 0 is u + P e on
-// B_0 (gmt_mg_prolong_smooth)
-static int mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
-                            const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
-                            double omega, double* out, int64_t ldo, const HostProlong* pro = nullptr) {
-  if (k < 1 || k > GMT_MG_MAX_FUSE || halo_mask < 0 || halo_mask > 15) return 1;
-  if (nx < 0 || ny < 0) return 1;
-  if (nx == 0 || ny == 0) return 0;
+// k sweeps on a region whose arguments passed their check.  rb: only the cells due in half-sweep j are updated
+// (gmt_mg_smooth_rb's colour rule); pro: level 0 is u + P e on B_0 (gmt_mg_prolong_smooth)
+static void mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
+                             const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
+                             double omega, double* out, int64_t ldo, const HostProlong* pro = nullptr) {
   const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
              hn = halo_mask & GMT_MG_HALO_N;
-  const int64_t gw = hw ? k : 1, ge = he ? k : 1, gs = hs ? k : 1, gn = hn ? k : 1;
-  if (!u || !out || x0 < gw || y0 < gs || ld < x0 + nx + ge || ldo < x0 + nx || (f && ldf < x0 + nx + (ge - 1)))
-    return 1;
-  {  // u's read set against out[R], as address ranges
-    const double* ua = u + (y0 - gs) * ld + (x0 - gw);
-    const double* ub = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
-    const double* oa = out + y0 * ldo + x0;
-    const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
-    if (ua < oe && oa < ub) return 1;
-  }
+  const gmt::MgSides g = gmt::mg_sides(halo_mask, k, 1);
+  const int64_t gw = g.w, ge = g.e, gs = g.s, gn = g.n;
   // w: the read set, cell (0, 0) at (x0 - gw, y0 - gs); t: the level being computed
   const int64_t wx = nx + gw + ge, wy = ny + gs + gn;
   std::vector<double> w(static_cast<size_t>(wx * wy)), t;
@@ -561,13 +551,15 @@ static int mg_smooth_levels(int k, bool rb, int par, int64_t x0, int64_t nx, int
   }
   for (int64_t y = 0; y < ny; ++y)
     for (int64_t x = 0; x < nx; ++x) out[(y0 + y) * ldo + x0 + x] = w[(gs + y) * wx + gw + x];
-  return 0;
 }
 
 int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u, int64_t ld,
                     const double* f, int64_t ldf, double c0, double c1, double omega, double* out, int64_t ldo,
                     void*) {
-  return mg_smooth_levels(k, false, 0, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
+  const MgCheck chk = gmt::mg_fuse_check(k, 0, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
+  mg_smooth_levels(k, false, 0, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
+  return 0;
 }
 
 // h coloured half-sweeps: the same definition with the colour rule
@@ -580,17 +572,17 @@ int gmt_mg_smooth_rb_path(int, int, int64_t, int64_t, int64_t, int, const double
 int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u,
                      int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
                      int64_t ldo, void*) {
-  if (par < 0 || par > 1) return 1;
-  return mg_smooth_levels(h, true, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
+  const MgCheck chk = gmt::mg_fuse_check(h, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
+  mg_smooth_levels(h, true, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo);
+  return 0;
 }
 
 int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* d, int64_t ldd,
                     double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void*) {
-  if (nx < 0 || ny < 0) return 1;
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (!d || !sc || x0 < 1 || y0 < 1 || cx0 < 0 || cy0 < 0 || ldd < x0 + nx + 1 || ldc < cx0 + mx) return 1;
+  int64_t mx, my;
+  const MgCheck chk = gmt::mg_restrict_check(x0, nx, y0, ny, px, py, d, ldd, sc, cx0, cy0, ldc, &mx, &my);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   auto h = [](const double* p) {
     const double t = 2.0 * p[0];
     return (p[-1] + p[1]) + t;
@@ -619,34 +611,16 @@ int gmt_mg_resid_restrict_path(int64_t, int64_t, int64_t, int64_t, int, int, int
 int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
                           const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1, double cs,
                           double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void*) {
-  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0) return 1;
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
-  const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
-             hn = halo_mask & GMT_MG_HALO_N;
-  const int64_t gw = hw ? 2 : 1, ge = he ? 2 : 1, gs = hs ? 2 : 1, gn = hn ? 2 : 1;
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (!u || !sc || x0 < gw || y0 < gs || cx0 < 0 || cy0 < 0 || ld < x0 + nx + ge || ldc < cx0 + mx ||
-      (f && ldf < x0 + nx + (ge - 1)))
-    return 1;
-  if (mx == 0 || my == 0) return 0;
-  {  // the read sets of u and f against sc's cells, as address ranges
-    const double* oa = sc + cy0 * ldc + cx0;
-    const double* oe = sc + (cy0 + my - 1) * ldc + (cx0 + mx);
-    const double* ua = u + (y0 - gs) * ld + (x0 - gw);
-    const double* ue = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
-    if (ua < oe && oa < ue) return 1;
-    if (f) {
-      const double* fa = f + (y0 - (gs - 1)) * ldf + (x0 - (gw - 1));
-      const double* fe = f + (y0 + ny + gn - 2) * ldf + (x0 + nx + ge - 1);
-      if (fa < oe && oa < fe) return 1;
-    }
-  }
+  int64_t mx, my;
+  const MgCheck chk = gmt::mg_resid_restrict_check(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc,
+                                                   &mx, &my);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
+  const gmt::MgSides b = gmt::mg_sides(halo_mask, 1, 0);  // the grown box: one cell on a halo side
   // d: the region and its ring, cell (0, 0) at (x0 - 1, y0 - 1); the residual on the grown box
   const int64_t wx = nx + 2, wy = ny + 2;
   std::vector<double> d(static_cast<size_t>(wx * wy), 0.0);
-  for (int64_t y = y0 - (hs ? 1 : 0); y < y0 + ny + (hn ? 1 : 0); ++y)
-    for (int64_t x = x0 - (hw ? 1 : 0); x < x0 + nx + (he ? 1 : 0); ++x) {
+  for (int64_t y = y0 - b.s; y < y0 + ny + b.n; ++y)
+    for (int64_t x = x0 - b.w; x < x0 + nx + b.e; ++x) {
       const double* c = u + y * ld + x;  // gmt_cg_apply mode 1's cell
       double o = c0 * ((c[-1] + c[1]) + (c[-ld] + c[ld]));
       if (f) o = o + c1 * f[y * ldf + x];
@@ -657,11 +631,8 @@ int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px
 
 int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, const double* e, int64_t cx0,
                        int64_t cy0, int64_t lde, double* u, int64_t ld, void*) {
-  if (nx < 0 || ny < 0) return 1;
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return 1;
-  const int64_t mx = (nx - px + 1) / 2;
-  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < 1 || cy0 < 1 || lde < cx0 + mx + 1 || ld < x0 + nx) return 1;
+  const MgCheck chk = gmt::mg_prolong_add_check(x0, nx, y0, ny, px, py, e, cx0, cy0, lde, u, ld);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   for (int64_t j = 0; j < ny; ++j)
     for (int64_t i = 0; i < nx; ++i) {
       double* q = u + (y0 + j) * ld + x0 + i;
@@ -686,33 +657,12 @@ int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t nx, int64_
                           int halo_mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
                           int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega, double* out,
                           int64_t ldo, void*) {
-  if (h < 1 || h > GMT_MG_MAX_FUSE || rb < 0 || rb > 1 || par < 0 || par > 1 || px < 0 || px > 1 || py < 0 ||
-      py > 1 || halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0)
-    return 1;
-  if (nx == 0 || ny == 0) return 0;
-  if (!e || !out) return 1;
-  const bool hw = halo_mask & GMT_MG_HALO_W, he = halo_mask & GMT_MG_HALO_E, hs = halo_mask & GMT_MG_HALO_S,
-             hn = halo_mask & GMT_MG_HALO_N;
-  // the coarse cells that may be read: h/2 + 1 beyond the region's on a halo side, the ring on the others
-  const int64_t d = h / 2 + 1, cw = hw ? d : 1, ce = he ? d : 1, cs = hs ? d : 1, cn = hn ? d : 1;
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (cx0 < cw || cy0 < cs || lde < cx0 + mx + ce) return 1;
-  if (x0 < 1 || y0 < 1 || ldo < x0 + nx) return 1;  // before out's addresses are formed
-  {  // out[R] against the read sets of e and f, as address ranges (u's: mg_smooth_levels)
-    const double* oa = out + y0 * ldo + x0;
-    const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
-    const double* ea = e + (cy0 - cs) * lde + (cx0 - cw);
-    const double* ee = e + (cy0 + my + cn - 1) * lde + (cx0 + mx + ce);
-    if (ea < oe && oa < ee) return 1;
-    if (f) {
-      const int64_t gw = hw ? h - 1 : 0, ge = he ? h - 1 : 0, gs = hs ? h - 1 : 0, gn = hn ? h - 1 : 0;
-      const double* fa = f + (y0 - gs) * ldf + (x0 - gw);
-      const double* fe = f + (y0 + ny + gn - 1) * ldf + (x0 + nx + ge);
-      if (fa < oe && oa < fe) return 1;
-    }
-  }
+  const MgCheck chk = gmt::mg_prolong_smooth_check(h, rb, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u,
+                                                   ld, f, ldf, out, ldo, nullptr);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   const HostProlong pro{e + cy0 * lde + cx0, lde, px, py};
-  return mg_smooth_levels(h, rb != 0, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, &pro);
+  mg_smooth_levels(h, rb != 0, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, &pro);
+  return 0;
 }
 
 // the table-driven transfers: the plan is the host's tables themselves
@@ -748,10 +698,8 @@ int gmt_mg_restrict_tab(const void* plan, int64_t x0, int64_t y0, const double* 
   const auto* p = static_cast<const HostXferPlan*>(plan);
   if (!p) return 1;
   const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0], my = p->cn[1];
-  if (nx == 0 || ny == 0 || mx == 0 || my == 0) return 0;
-  if (!d || !sc || x0 < gmt::kMgTapHalo || y0 < gmt::kMgTapHalo || cx0 < 0 || cy0 < 0 ||
-      ldd < x0 + nx + gmt::kMgTapHalo || ldc < cx0 + mx)
-    return 1;
+  const MgCheck chk = gmt::mg_restrict_tab_check(nx, ny, mx, my, x0, y0, d, ldd, sc, cx0, cy0, ldc);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   const gmt::MgAxisTab &tx = p->tab[0], &ty = p->tab[1];
   auto h = [](const double* q, const double* w, int cnt) {
     const double a0 = w[0] * q[0], a1 = w[1] * q[1], a2 = w[2] * q[2];
@@ -783,10 +731,8 @@ int gmt_mg_prolong_add_tab(const void* plan, int64_t x0, int64_t y0, const doubl
   const auto* p = static_cast<const HostXferPlan*>(plan);
   if (!p) return 1;
   const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0];
-  if (nx == 0 || ny == 0) return 0;
-  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < gmt::kMgRingHalo || cy0 < gmt::kMgRingHalo ||
-      lde < cx0 + mx + gmt::kMgRingHalo || ld < x0 + nx)
-    return 1;
+  const MgCheck chk = gmt::mg_prolong_add_tab_check(nx, ny, mx, x0, y0, e, cx0, cy0, lde, u, ld);
+  if (chk != MgCheck::kRun) return gmt::mg_check_code(chk, 1);
   const gmt::MgAxisTab &tx = p->tab[0], &ty = p->tab[1];
   for (int64_t j = 0; j < ny; ++j)
     for (int64_t i = 0; i < nx; ++i) {

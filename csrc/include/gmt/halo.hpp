@@ -212,6 +212,12 @@ class Halo2D {
     }
     watchdog_kick("halo exchange");
   }
+  // The whole exchange in stream order, without blocking; nothing on a plan
+  // without neighbours.
+  void enqueue(gmt_stream_t s) {
+    start(s);
+    finish(s);
+  }
   // Blocking exchange, reference semantics: ghosts valid and the stream
   // drained on return.
   void exchange(gmt_stream_t s) {

@@ -45,12 +45,22 @@
 #include "common.hpp"
 #include "row_walk.hpp"
 #include "gmt/kernels.h"
+#include "gmt/mg_args.hpp"
 #include "gmt/mg_tab.hpp"
 
 namespace gmt {
 
 // row loads in flight per lane (as the Chebyshev step's)
 constexpr int kMgUnrollP = 4, kMgUnrollF = 2;
+
+constexpr int kMgRefuse = static_cast<int>(hipErrorInvalidValue);  // what a refused check (gmt/mg_args.hpp) returns
+
+// the grid of a kernel with one lane per cell or per pair; false past the grid's x extent
+static bool mg_lane_grid(int64_t lanes, unsigned* grid) {
+  const int64_t nb = (lanes + kBlock - 1) / kBlock;
+  *grid = grid_1d(nb);
+  return nb <= INT32_MAX;
+}
 
 template <bool HAS_F>
 __device__ __forceinline__ double mg_smooth_cell(double w, double e, double n, double s, double u, double c0,
@@ -124,13 +134,13 @@ static int mg_smooth_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64
   if (walk) {
     int64_t nseg, L;
     const int64_t nb = walk_blocks(nx, ny, &nseg, &L);
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
+    if (nb > INT32_MAX) return kMgRefuse;  // the grid's x extent
     mg_smooth_walk<HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, om, out, ldo, nseg, L,
                                                          nb);
   } else {
-    const int64_t nb = (nx * ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_smooth_scalar<HAS_F><<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, om, out, ldo);
+    unsigned grid;
+    if (!mg_lane_grid(nx * ny, &grid)) return kMgRefuse;
+    mg_smooth_scalar<HAS_F><<<grid, kBlock, 0, s>>>(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, om, out, ldo);
   }
   GMT_RET_LAUNCH();
 }
@@ -166,15 +176,14 @@ static int mg_smooth_launch(bool walk, int64_t x0, int64_t nx, int64_t y0, int64
 //                       evaluating the due cell alone, operands by selects,
 //                       measured the same (profiles/mg_rb).
 
-constexpr int kMgMaxFuse = GMT_MG_MAX_FUSE;
 // the shortest segment: 4k rows rounded up to a power of two, so the 2k warm-up
 // rows stay at half the segment or below.  Small levels want short segments:
 // a wave walks its rows one after another, and with 32-row segments the
 // levels from 4095² down took longer fused than sweep by sweep.
 constexpr int64_t mg_fuse_min_seg(int k) { return k <= 2 ? 8 : 16; }
 
-constexpr int mg_fuse_shift(int k) { return k / 2 * 2; }  // k - 1 rounded up to even
-constexpr int mg_fuse_wave_cols(int k) { return k == 1 ? kWalkWaveCols : kWalkWaveCols - 2 * mg_fuse_shift(k); }
+// mg_fuse_shift and mg_fuse_wave_cols: gmt/mg_args.hpp, which the CPU backend reports the geometry from
+static_assert(kMgWaveCols == kWalkWaveCols && kMgBlockWaves == kBlock / kWave, "gmt/mg_args.hpp: the walk's geometry");
 
 struct MgFuseArgs {
   int64_t x0, nx, y0, ny;
@@ -465,48 +474,59 @@ __global__ __launch_bounds__(kBlock) void mg_smooth_k_scalar(const MgWalkArgs<PR
 
 // rows per segment of the fused walk: the row walk's rule with its own floor
 static int64_t mg_fuse_seg_rows(int k, int64_t nx, int64_t ny) {
-  const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(k)) * (kBlock / kWave);
-  const int64_t nbx = (nx + bc - 1) / bc;
+  const int64_t nbx = (nx + mg_fuse_block_cols(k) - 1) / mg_fuse_block_cols(k);
   int64_t L = kWalkMaxSeg;
   while (L > mg_fuse_min_seg(k) && nbx * ((ny + L - 1) / L) < 8 * static_cast<int64_t>(walk_cus())) L /= 2;
   return L;
 }
 
-// gmt_mg_smooth_k takes these arguments (a non-empty region, k and the mask in range)
-static bool mg_fuse_args_ok(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int mask, const double* u,
-                            int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo) {
-  const int64_t gw = mask & GMT_MG_HALO_W ? k : 1, ge = mask & GMT_MG_HALO_E ? k : 1;
-  const int64_t gs = mask & GMT_MG_HALO_S ? k : 1, gn = mask & GMT_MG_HALO_N ? k : 1;
-  if (!u || !out || x0 < gw || y0 < gs || ld < x0 + nx + ge || ldo < x0 + nx || (f && ldf < x0 + nx + (ge - 1)))
-    return false;
-  // u's read set against out[R], as address ranges
-  const double* ua = u + (y0 - gs) * ld + (x0 - gw);
-  const double* ub = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
-  const double* oa = out + y0 * ldo + x0;
-  const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
-  return !(ua < oe && oa < ub);
+// the grid of a fused walk of depth k over a's region, into a; false past the grid's x extent
+template <class Args>
+static bool mg_fuse_grid(int k, Args* a) {
+  a->seg_rows = mg_fuse_seg_rows(k, a->nx, a->ny);
+  a->nseg = (a->ny + a->seg_rows - 1) / a->seg_rows;
+  a->nblocks = (a->nx + mg_fuse_block_cols(k) - 1) / mg_fuse_block_cols(k) * a->nseg;
+  return a->nblocks <= INT32_MAX;
 }
 
-template <int K, bool HAS_F, bool RB = false, bool PR = false>
+// what a _path call reports once its path is decided: the segment rows of the walk of depth k, 0 off the walk
+static int mg_fuse_path(int path, int k, int64_t nx, int64_t ny, int64_t* seg_rows) {
+  if (seg_rows) *seg_rows = path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0 ? mg_fuse_seg_rows(k, nx, ny) : 0;
+  return path;
+}
+
+template <int K, bool HAS_F, bool RB, bool PR>
 static int mg_smooth_k_launch(bool walk, MgWalkArgs<PR> a, hipStream_t s) {
   if (walk) {
-    const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(K)) * (kBlock / kWave);
-    a.seg_rows = mg_fuse_seg_rows(K, a.nx, a.ny);
-    a.nseg = (a.ny + a.seg_rows - 1) / a.seg_rows;
-    a.nblocks = (a.nx + bc - 1) / bc * a.nseg;
-    if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
+    if (!mg_fuse_grid(K, &a)) return kMgRefuse;
     mg_smooth_k_walk<K, HAS_F, RB, PR><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
   } else {
-    const int64_t nb = (a.nx * a.ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_smooth_k_scalar<K, HAS_F, RB, PR><<<grid_1d(nb), kBlock, 0, s>>>(a);
+    unsigned grid;
+    if (!mg_lane_grid(a.nx * a.ny, &grid)) return kMgRefuse;
+    mg_smooth_k_scalar<K, HAS_F, RB, PR><<<grid, kBlock, 0, s>>>(a);
   }
   GMT_RET_LAUNCH();
 }
 
-template <int K, bool RB = false, bool PR = false>
+template <int K, bool RB, bool PR>
 static int mg_smooth_k_launch_f(bool walk, const MgWalkArgs<PR>& a, hipStream_t s) {
   return a.f ? mg_smooth_k_launch<K, true, RB, PR>(walk, a, s) : mg_smooth_k_launch<K, false, RB, PR>(walk, a, s);
+}
+
+// k sweeps (RB: half-sweeps; PR: behind the interpolation) on the walk or one lane per cell.  Plain k = 1 is
+// gmt_mg_smooth's kernel and is not compiled here.
+template <bool RB, bool PR>
+static int mg_smooth_k_run(int k, const MgWalkArgs<PR>& a, hipStream_t s) {
+  static_assert(GMT_MG_MAX_FUSE == 4, "one case per depth");
+  const bool walk = mg_smooth_path(a.x0, a.u, a.ld, a.f, a.ldf, a.out, a.ldo) == GMT_PATH_ROW_WALK;
+  switch (k) {
+    case 1:
+      if constexpr (RB || PR) return mg_smooth_k_launch_f<1, RB, PR>(walk, a, s);  // one level: 16 B per point
+      return kMgRefuse;
+    case 2: return mg_smooth_k_launch_f<2, RB, PR>(walk, a, s);
+    case 3: return mg_smooth_k_launch_f<3, RB, PR>(walk, a, s);
+    default: return mg_smooth_k_launch_f<4, RB, PR>(walk, a, s);
+  }
 }
 
 // ---- full weighting ----
@@ -807,31 +827,6 @@ static int mg_resid_restrict_path(int64_t x0, int64_t cx0, const double* u, int6
              : GMT_PATH_SCALAR;
 }
 
-// gmt_mg_resid_restrict takes these arguments (a non-empty region, the mask and the parities in range)
-static bool mg_resid_restrict_args_ok(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int mask,
-                                      const double* u, int64_t ld, const double* f, int64_t ldf, const double* sc,
-                                      int64_t cx0, int64_t cy0, int64_t ldc) {
-  const int64_t gw = mask & GMT_MG_HALO_W ? 2 : 1, ge = mask & GMT_MG_HALO_E ? 2 : 1;
-  const int64_t gs = mask & GMT_MG_HALO_S ? 2 : 1, gn = mask & GMT_MG_HALO_N ? 2 : 1;
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (!u || !sc || x0 < gw || y0 < gs || cx0 < 0 || cy0 < 0 || ld < x0 + nx + ge || ldc < cx0 + mx ||
-      (f && ldf < x0 + nx + (ge - 1)))
-    return false;
-  if (mx == 0 || my == 0) return true;
-  // the read sets of u and f against sc's cells, as address ranges
-  const double* oa = sc + cy0 * ldc + cx0;
-  const double* oe = sc + (cy0 + my - 1) * ldc + (cx0 + mx);
-  const double* ua = u + (y0 - gs) * ld + (x0 - gw);
-  const double* ue = u + (y0 + ny + gn - 1) * ld + (x0 + nx + ge);
-  if (ua < oe && oa < ue) return false;
-  if (f) {
-    const double* fa = f + (y0 - (gs - 1)) * ldf + (x0 - (gw - 1));
-    const double* fe = f + (y0 + ny + gn - 2) * ldf + (x0 + nx + ge - 1);
-    if (fa < oe && oa < fe) return false;
-  }
-  return true;
-}
-
 static int mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc, int64_t ldc) {
   return x0 % 2 == 0 && cx0 % 2 == 0 && walk_vec_ok(d, ldd) && walk_vec_ok(sc, ldc) ? GMT_PATH_PT : GMT_PATH_SCALAR;
 }
@@ -1006,10 +1001,8 @@ extern "C" int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, con
                              int64_t ldo, void* stream) {
   using namespace gmt;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (!u || !out || x0 < 1 || y0 < 1 || ld < x0 + nx + 1 || ldo < x0 + nx || (f && ldf < x0 + nx))
-    return static_cast<int>(hipErrorInvalidValue);
+  const MgCheck c = mg_smooth_check(x0, nx, y0, ny, u, ld, f, ldf, out, ldo);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
   return f ? mg_smooth_launch<true>(walk, x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, s)
            : mg_smooth_launch<false>(walk, x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, s);
@@ -1017,9 +1010,9 @@ extern "C" int gmt_mg_smooth(int64_t x0, int64_t nx, int64_t y0, int64_t ny, con
 
 extern "C" int gmt_mg_smooth_k_geom(int k, int64_t* wave_cols, int64_t* block_cols) {
   using namespace gmt;
-  if (k < 1 || k > kMgMaxFuse) return static_cast<int>(hipErrorInvalidValue);
+  if (!mg_depth_ok(k)) return kMgRefuse;
   if (wave_cols) *wave_cols = mg_fuse_wave_cols(k);
-  if (block_cols) *block_cols = static_cast<int64_t>(mg_fuse_wave_cols(k)) * (kBlock / kWave);
+  if (block_cols) *block_cols = mg_fuse_block_cols(k);
   return 0;
 }
 
@@ -1027,117 +1020,41 @@ extern "C" int gmt_mg_smooth_k_path(int k, int64_t x0, int64_t nx, int64_t ny, i
                                     int64_t ld, const double* f, int64_t ldf, const double* out, int64_t ldo,
                                     int64_t* seg_rows) {
   using namespace gmt;
-  if (seg_rows) *seg_rows = 0;
-  if (k < 1 || k > kMgMaxFuse || halo_mask < 0 || halo_mask > 15) return GMT_PATH_NONE;
+  if (!mg_depth_ok(k) || !mg_mask_ok(halo_mask)) return mg_fuse_path(GMT_PATH_NONE, k, nx, ny, seg_rows);
   if (k == 1) return gmt_mg_smooth_path(x0, nx, ny, u, ld, f, ldf, out, ldo, seg_rows);
-  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);
-  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(k, nx, ny);
-  return path;
+  return mg_fuse_path(mg_smooth_path(x0, u, ld, f, ldf, out, ldo), k, nx, ny, seg_rows);
 }
 
 extern "C" int gmt_mg_smooth_k(int k, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask, const double* u,
                                int64_t ld, const double* f, int64_t ldf, double c0, double c1, double omega,
                                double* out, int64_t ldo, void* stream) {
   using namespace gmt;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (k < 1 || k > kMgMaxFuse || halo_mask < 0 || halo_mask > 15) return static_cast<int>(hipErrorInvalidValue);
-  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (!mg_fuse_args_ok(k, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo))
-    return static_cast<int>(hipErrorInvalidValue);
+  const MgCheck c = mg_fuse_check(k, 0, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   if (k == 1) return gmt_mg_smooth(x0, nx, y0, ny, u, ld, f, ldf, c0, c1, omega, out, ldo, stream);
-  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
   const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0, 0};
-  switch (k) {
-    case 2: return mg_smooth_k_launch_f<2>(walk, a, s);
-    case 3: return mg_smooth_k_launch_f<3>(walk, a, s);
-    default: return mg_smooth_k_launch_f<4>(walk, a, s);
-  }
+  return mg_smooth_k_run<false, false>(k, a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gmt_mg_smooth_rb_path(int h, int par, int64_t x0, int64_t nx, int64_t ny, int halo_mask,
                                      const double* u, int64_t ld, const double* f, int64_t ldf, const double* out,
                                      int64_t ldo, int64_t* seg_rows) {
   using namespace gmt;
-  if (seg_rows) *seg_rows = 0;
-  if (h < 1 || h > kMgMaxFuse || par < 0 || par > 1 || halo_mask < 0 || halo_mask > 15) return GMT_PATH_NONE;
-  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);
-  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(h, nx, ny);
-  return path;
+  const bool ok = mg_depth_ok(h) && mg_bit_ok(par) && mg_mask_ok(halo_mask);
+  return mg_fuse_path(ok ? mg_smooth_path(x0, u, ld, f, ldf, out, ldo) : GMT_PATH_NONE, h, nx, ny, seg_rows);
 }
 
 extern "C" int gmt_mg_smooth_rb(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int halo_mask,
                                 const double* u, int64_t ld, const double* f, int64_t ldf, double c0, double c1,
                                 double omega, double* out, int64_t ldo, void* stream) {
   using namespace gmt;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h < 1 || h > kMgMaxFuse || par < 0 || par > 1 || halo_mask < 0 || halo_mask > 15)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (!mg_fuse_args_ok(h, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo))
-    return static_cast<int>(hipErrorInvalidValue);
-  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
+  const MgCheck c = mg_fuse_check(h, par, x0, nx, y0, ny, halo_mask, u, ld, f, ldf, out, ldo);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   const MgFuseArgs a{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0, par};
-  switch (h) {
-    case 1: return mg_smooth_k_launch_f<1, true>(walk, a, s);  // the K-level walk with one level: 16 B per point
-    case 2: return mg_smooth_k_launch_f<2, true>(walk, a, s);
-    case 3: return mg_smooth_k_launch_f<3, true>(walk, a, s);
-    default: return mg_smooth_k_launch_f<4, true>(walk, a, s);
-  }
+  return mg_smooth_k_run<true, false>(h, a, static_cast<hipStream_t>(stream));
 }
 
 // ---- the interpolation fused into h sweeps or half-sweeps (gmt_mg_prolong_smooth) ----
-
-namespace gmt {
-
-// gmt_mg_prolong_smooth takes these arguments (a non-empty region; h, rb, par, px, py and the mask in range);
-// *a gets the launch's arguments
-static bool mg_prolong_smooth_args(int h, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py,
-                                   int mask, const double* e, int64_t cx0, int64_t cy0, int64_t lde, const double* u,
-                                   int64_t ld, const double* f, int64_t ldf, double c0, double c1, double om,
-                                   double* out, int64_t ldo, MgProArgs* a) {
-  if (!e || !mg_fuse_args_ok(h, x0, nx, y0, ny, mask, u, ld, f, ldf, out, ldo)) return false;
-  // the coarse cells that may be read: h/2 + 1 beyond the region's on a halo side, the ring on the others
-  const int64_t d = h / 2 + 1;
-  const int64_t cw = mask & GMT_MG_HALO_W ? d : 1, ce = mask & GMT_MG_HALO_E ? d : 1;
-  const int64_t cs = mask & GMT_MG_HALO_S ? d : 1, cn = mask & GMT_MG_HALO_N ? d : 1;
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (cx0 < cw || cy0 < cs || lde < cx0 + mx + ce) return false;
-  // out[R] against the read sets of e and f, as address ranges (u's: mg_fuse_args_ok)
-  const double* oa = out + y0 * ldo + x0;
-  const double* oe = out + (y0 + ny - 1) * ldo + (x0 + nx);
-  const double* ea = e + (cy0 - cs) * lde + (cx0 - cw);
-  const double* ee = e + (cy0 + my + cn - 1) * lde + (cx0 + mx + ce);
-  if (ea < oe && oa < ee) return false;
-  if (f) {
-    const int64_t gw = mask & GMT_MG_HALO_W ? h - 1 : 0, ge = mask & GMT_MG_HALO_E ? h - 1 : 0;
-    const int64_t gs = mask & GMT_MG_HALO_S ? h - 1 : 0, gn = mask & GMT_MG_HALO_N ? h - 1 : 0;
-    const double* fa = f + (y0 - gs) * ldf + (x0 - gw);
-    const double* fe = f + (y0 + ny + gn - 1) * ldf + (x0 + nx + ge);
-    if (fa < oe && oa < fe) return false;
-  }
-  if (a) {
-    static_cast<MgFuseArgs&>(*a) = MgFuseArgs{x0, nx, y0, ny, mask, u, ld, f, ldf, c0, c1, om, out, ldo, 0, 0, 0, par};
-    a->e = e + cy0 * lde + cx0;
-    a->lde = lde;
-    a->px = px, a->py = py;
-    a->ilo = -cw, a->ihi = mx - 1 + ce, a->jlo = -cs, a->jhi = my - 1 + cn;
-  }
-  return true;
-}
-
-static bool mg_prolong_smooth_range(int h, int rb, int par, int px, int py, int mask) {
-  return h >= 1 && h <= kMgMaxFuse && rb >= 0 && rb <= 1 && par >= 0 && par <= 1 && px >= 0 && px <= 1 && py >= 0 &&
-         py <= 1 && mask >= 0 && mask <= 15;
-}
-
-template <int K>
-static int mg_prolong_smooth_launch(bool rb, bool walk, const MgProArgs& a, hipStream_t s) {
-  return rb ? mg_smooth_k_launch_f<K, true, true>(walk, a, s) : mg_smooth_k_launch_f<K, false, true>(walk, a, s);
-}
-
-}  // namespace gmt
 
 extern "C" int gmt_mg_prolong_smooth_geom(int h, int64_t* wave_cols, int64_t* block_cols) {
   return gmt_mg_smooth_k_geom(h, wave_cols, block_cols);
@@ -1148,15 +1065,10 @@ extern "C" int gmt_mg_prolong_smooth_path(int h, int rb, int par, int64_t x0, in
                                           int64_t lde, const double* u, int64_t ld, const double* f, int64_t ldf,
                                           const double* out, int64_t ldo, int64_t* seg_rows) {
   using namespace gmt;
-  if (seg_rows) *seg_rows = 0;
-  if (!mg_prolong_smooth_range(h, rb, par, px, py, halo_mask) || nx < 0 || ny < 0) return GMT_PATH_NONE;
-  if (nx > 0 && ny > 0 &&
-      !mg_prolong_smooth_args(h, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f, ldf, 0.0, 0.0, 0.0,
-                              const_cast<double*>(out), ldo, nullptr))
-    return GMT_PATH_NONE;
-  const int path = mg_smooth_path(x0, u, ld, f, ldf, out, ldo);  // e is read 8 B per lane: no rule of its own
-  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(h, nx, ny);
-  return path;
+  const bool ok = mg_prolong_smooth_check(h, rb, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f,
+                                          ldf, out, ldo, nullptr) != MgCheck::kRefuse;
+  // e is read 8 B per lane: no rule of its own
+  return mg_fuse_path(ok ? mg_smooth_path(x0, u, ld, f, ldf, out, ldo) : GMT_PATH_NONE, h, nx, ny, seg_rows);
 }
 
 extern "C" int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px,
@@ -1165,20 +1077,13 @@ extern "C" int gmt_mg_prolong_smooth(int h, int rb, int par, int64_t x0, int64_t
                                      double omega, double* out, int64_t ldo, void* stream) {
   using namespace gmt;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!mg_prolong_smooth_range(h, rb, par, px, py, halo_mask) || nx < 0 || ny < 0)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  MgProArgs a;
-  if (!mg_prolong_smooth_args(h, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f, ldf, c0, c1,
-                              omega, out, ldo, &a))
-    return static_cast<int>(hipErrorInvalidValue);
-  const bool walk = mg_smooth_path(x0, u, ld, f, ldf, out, ldo) == GMT_PATH_ROW_WALK;
-  switch (h) {
-    case 1: return mg_prolong_smooth_launch<1>(rb != 0, walk, a, s);
-    case 2: return mg_prolong_smooth_launch<2>(rb != 0, walk, a, s);
-    case 3: return mg_prolong_smooth_launch<3>(rb != 0, walk, a, s);
-    default: return mg_prolong_smooth_launch<4>(rb != 0, walk, a, s);
-  }
+  MgCoarseWin w;
+  const MgCheck c = mg_prolong_smooth_check(h, rb, par, x0, nx, y0, ny, px, py, halo_mask, e, cx0, cy0, lde, u, ld, f,
+                                            ldf, out, ldo, &w);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
+  const MgProArgs a{{x0, nx, y0, ny, halo_mask, u, ld, f, ldf, c0, c1, omega, out, ldo, 0, 0, 0, par},
+                    e + cy0 * lde + cx0, lde, px, py, w.ilo, w.ihi, w.jlo, w.jhi};
+  return rb ? mg_smooth_k_run<true, true>(h, a, s) : mg_smooth_k_run<false, true>(h, a, s);
 }
 
 extern "C" int gmt_mg_restrict_path(int64_t x0, int64_t cx0, const double* d, int64_t ldd, const double* sc,
@@ -1191,22 +1096,16 @@ extern "C" int gmt_mg_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, i
                                void* stream) {
   using namespace gmt;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return static_cast<int>(hipErrorInvalidValue);
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (!d || !sc || x0 < 1 || y0 < 1 || cx0 < 0 || cy0 < 0 || ldd < x0 + nx + 1 || ldc < cx0 + mx)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (mx == 0 || my == 0) return 0;  // no coarse point on the region
-  if (mg_restrict_path(x0, cx0, d, ldd, sc, ldc) == GMT_PATH_PT) {
-    const int64_t nb = ((mx + 1) / 2 * my + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_restrict_pt<<<grid_1d(nb), kBlock, 0, s>>>(x0, y0, px, py, mx, my, d, ldd, cs, sc, cx0, cy0, ldc);
-  } else {
-    const int64_t nb = (mx * my + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_restrict_scalar<<<grid_1d(nb), kBlock, 0, s>>>(x0, y0, px, py, mx, my, d, ldd, cs, sc, cx0, cy0, ldc);
-  }
+  int64_t mx, my;
+  const MgCheck c = mg_restrict_check(x0, nx, y0, ny, px, py, d, ldd, sc, cx0, cy0, ldc, &mx, &my);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
+  const bool pt = mg_restrict_path(x0, cx0, d, ldd, sc, ldc) == GMT_PATH_PT;
+  unsigned grid;
+  if (!mg_lane_grid((pt ? (mx + 1) / 2 : mx) * my, &grid)) return kMgRefuse;
+  if (pt)
+    mg_restrict_pt<<<grid, kBlock, 0, s>>>(x0, y0, px, py, mx, my, d, ldd, cs, sc, cx0, cy0, ldc);
+  else
+    mg_restrict_scalar<<<grid, kBlock, 0, s>>>(x0, y0, px, py, mx, my, d, ldd, cs, sc, cx0, cy0, ldc);
   GMT_RET_LAUNCH();
 }
 
@@ -1219,14 +1118,13 @@ extern "C" int gmt_mg_resid_restrict_path(int64_t x0, int64_t nx, int64_t y0, in
                                           const double* sc, int64_t cx0, int64_t cy0, int64_t ldc,
                                           int64_t* seg_rows) {
   using namespace gmt;
-  if (seg_rows) *seg_rows = 0;
-  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0 || px < 0 || px > 1 || py < 0 || py > 1)
-    return GMT_PATH_NONE;
-  if (nx > 0 && ny > 0 && !mg_resid_restrict_args_ok(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc))
-    return GMT_PATH_NONE;
-  const int path = mg_resid_restrict_path(x0, cx0, u, ld, f, ldf, sc, ldc);
-  if (seg_rows && path == GMT_PATH_ROW_WALK && nx > 0 && ny > 0) *seg_rows = mg_fuse_seg_rows(2, nx, ny);
-  return path;
+  int64_t mx, my;
+  // the parities count here on an empty region too
+  const bool ok = mg_bit_ok(px) && mg_bit_ok(py) &&
+                  mg_resid_restrict_check(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc, &mx,
+                                          &my) != MgCheck::kRefuse;
+  return mg_fuse_path(ok ? mg_resid_restrict_path(x0, cx0, u, ld, f, ldf, sc, ldc) : GMT_PATH_NONE, 2, nx, ny,
+                      seg_rows);
 }
 
 extern "C" int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t ny, int px, int py, int halo_mask,
@@ -1234,31 +1132,24 @@ extern "C" int gmt_mg_resid_restrict(int64_t x0, int64_t nx, int64_t y0, int64_t
                                      double cs, double* sc, int64_t cx0, int64_t cy0, int64_t ldc, void* stream) {
   using namespace gmt;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (halo_mask < 0 || halo_mask > 15 || nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return static_cast<int>(hipErrorInvalidValue);
-  if (!mg_resid_restrict_args_ok(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc))
-    return static_cast<int>(hipErrorInvalidValue);
-  const int64_t mx = (nx - px + 1) / 2, my = (ny - py + 1) / 2;
-  if (mx == 0 || my == 0) return 0;  // no coarse point on the region
+  int64_t mx, my;
+  const MgCheck c = mg_resid_restrict_check(x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, sc, cx0, cy0, ldc, &mx,
+                                            &my);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   MgRrArgs a{x0, nx, y0, ny, px, py, halo_mask, u, ld, f, ldf, c0, c1, cs, sc, cx0, cy0, ldc, mx, my, 0, 0, 0};
   if (mg_resid_restrict_path(x0, cx0, u, ld, f, ldf, sc, ldc) == GMT_PATH_ROW_WALK) {
-    const int64_t bc = static_cast<int64_t>(mg_fuse_wave_cols(2)) * (kBlock / kWave);
-    a.seg_rows = mg_fuse_seg_rows(2, nx, ny);
-    a.nseg = (ny + a.seg_rows - 1) / a.seg_rows;
-    a.nblocks = (nx + bc - 1) / bc * a.nseg;
-    if (a.nblocks > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);  // the grid's x extent
+    if (!mg_fuse_grid(2, &a)) return kMgRefuse;
     if (f)
       mg_resid_restrict_walk<true><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
     else
       mg_resid_restrict_walk<false><<<grid_1d(a.nblocks), kBlock, 0, s>>>(a);
   } else {
-    const int64_t nb = (mx * my + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
+    unsigned grid;
+    if (!mg_lane_grid(mx * my, &grid)) return kMgRefuse;
     if (f)
-      mg_resid_restrict_scalar<true><<<grid_1d(nb), kBlock, 0, s>>>(a);
+      mg_resid_restrict_scalar<true><<<grid, kBlock, 0, s>>>(a);
     else
-      mg_resid_restrict_scalar<false><<<grid_1d(nb), kBlock, 0, s>>>(a);
+      mg_resid_restrict_scalar<false><<<grid, kBlock, 0, s>>>(a);
   }
   GMT_RET_LAUNCH();
 }
@@ -1271,22 +1162,16 @@ extern "C" int gmt_mg_prolong_add(int64_t x0, int64_t nx, int64_t y0, int64_t ny
                                   int64_t cx0, int64_t cy0, int64_t lde, double* u, int64_t ld, void* stream) {
   using namespace gmt;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nx < 0 || ny < 0) return static_cast<int>(hipErrorInvalidValue);
-  if (nx == 0 || ny == 0) return 0;
-  if (px < 0 || px > 1 || py < 0 || py > 1) return static_cast<int>(hipErrorInvalidValue);
-  const int64_t mx = (nx - px + 1) / 2;
-  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < 1 || cy0 < 1 || lde < cx0 + mx + 1 || ld < x0 + nx)
-    return static_cast<int>(hipErrorInvalidValue);
+  const MgCheck c = mg_prolong_add_check(x0, nx, y0, ny, px, py, e, cx0, cy0, lde, u, ld);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   const double* e0 = e + cy0 * lde + cx0;
-  if (mg_prolong_path(x0, e, lde, u, ld) == GMT_PATH_PT) {
-    const int64_t nb = ((nx + 1) / 2 * ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_prolong_pt<<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, px, py, e0, lde, u, ld);
-  } else {
-    const int64_t nb = (nx * ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_prolong_scalar<<<grid_1d(nb), kBlock, 0, s>>>(x0, nx, y0, ny, px, py, e0, lde, u, ld);
-  }
+  const bool pt = mg_prolong_path(x0, e, lde, u, ld) == GMT_PATH_PT;
+  unsigned grid;
+  if (!mg_lane_grid((pt ? (nx + 1) / 2 : nx) * ny, &grid)) return kMgRefuse;
+  if (pt)
+    mg_prolong_pt<<<grid, kBlock, 0, s>>>(x0, nx, y0, ny, px, py, e0, lde, u, ld);
+  else
+    mg_prolong_scalar<<<grid, kBlock, 0, s>>>(x0, nx, y0, ny, px, py, e0, lde, u, ld);
   GMT_RET_LAUNCH();
 }
 
@@ -1360,22 +1245,17 @@ extern "C" int gmt_mg_restrict_tab(const void* plan, int64_t x0, int64_t y0, con
   const auto* p = static_cast<const MgXferPlan*>(plan);
   if (!p) return static_cast<int>(hipErrorInvalidValue);
   const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0], my = p->cn[1];
-  if (nx == 0 || ny == 0 || mx == 0 || my == 0) return 0;
-  if (!d || !sc || x0 < kMgTapHalo || y0 < kMgTapHalo || cx0 < 0 || cy0 < 0 || ldd < x0 + nx + kMgTapHalo ||
-      ldc < cx0 + mx)
-    return static_cast<int>(hipErrorInvalidValue);
+  const MgCheck c = mg_restrict_tab_check(nx, ny, mx, my, x0, y0, d, ldd, sc, cx0, cy0, ldc);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   const double* d0 = d + y0 * ldd + x0;
   double* s0 = sc + cy0 * ldc + cx0;
-  if (mg_restrict_path(x0, cx0, d, ldd, sc, ldc) == GMT_PATH_PT) {
-    const int64_t nb = ((mx + 1) / 2 * 2 * my + kBlock - 1) / kBlock;  // a lane per coarse cell, rows padded to pairs
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_restrict_tab_pt<<<grid_1d(nb), kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0, ldc);
-  } else {
-    const int64_t nb = (mx * my + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_restrict_tab_scalar<<<grid_1d(nb), kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0,
-                                                          ldc);
-  }
+  const bool pt = mg_restrict_path(x0, cx0, d, ldd, sc, ldc) == GMT_PATH_PT;
+  unsigned grid;  // pt: a lane per coarse cell, rows padded to pairs
+  if (!mg_lane_grid((pt ? (mx + 1) / 2 * 2 : mx) * my, &grid)) return kMgRefuse;
+  if (pt)
+    mg_restrict_tab_pt<<<grid, kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0, ldc);
+  else
+    mg_restrict_tab_scalar<<<grid, kBlock, 0, s>>>(mx, my, p->rf[0], p->rw[0], p->rf[1], p->rw[1], d0, ldd, s0, ldc);
   GMT_RET_LAUNCH();
 }
 
@@ -1390,21 +1270,16 @@ extern "C" int gmt_mg_prolong_add_tab(const void* plan, int64_t x0, int64_t y0, 
   const auto* p = static_cast<const MgXferPlan*>(plan);
   if (!p) return static_cast<int>(hipErrorInvalidValue);
   const int64_t nx = p->fn[0], ny = p->fn[1], mx = p->cn[0];
-  if (nx == 0 || ny == 0) return 0;
-  if (!e || !u || x0 < 1 || y0 < 1 || cx0 < kMgRingHalo || cy0 < kMgRingHalo || lde < cx0 + mx + kMgRingHalo ||
-      ld < x0 + nx)
-    return static_cast<int>(hipErrorInvalidValue);
+  const MgCheck c = mg_prolong_add_tab_check(nx, ny, mx, x0, y0, e, cx0, cy0, lde, u, ld);
+  if (c != MgCheck::kRun) return mg_check_code(c, kMgRefuse);
   const double* e0 = e + cy0 * lde + cx0;
   double* u0 = u + y0 * ld + x0;
-  if (mg_prolong_path(x0, e, lde, u, ld) == GMT_PATH_PT) {
-    const int64_t nb = ((nx + 1) / 2 * ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_prolong_tab_pt<<<grid_1d(nb), kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0, ld);
-  } else {
-    const int64_t nb = (nx * ny + kBlock - 1) / kBlock;
-    if (nb > INT32_MAX) return static_cast<int>(hipErrorInvalidValue);
-    mg_prolong_tab_scalar<<<grid_1d(nb), kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0,
-                                                         ld);
-  }
+  const bool pt = mg_prolong_path(x0, e, lde, u, ld) == GMT_PATH_PT;
+  unsigned grid;
+  if (!mg_lane_grid((pt ? (nx + 1) / 2 : nx) * ny, &grid)) return kMgRefuse;
+  if (pt)
+    mg_prolong_tab_pt<<<grid, kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0, ld);
+  else
+    mg_prolong_tab_scalar<<<grid, kBlock, 0, s>>>(nx, ny, p->pq[0], p->pt[0], p->pq[1], p->pt[1], e0, lde, u0, ld);
   GMT_RET_LAUNCH();
 }
